@@ -27,7 +27,10 @@ Default mode (``--mode transcribe``): one "step" = one full pass of model.transc
 Weak scaling: every rank processes its own recording; value = N * K * seconds / max-over-ranks wall time.  The default
 regrouping is part of the timed pass; ``config.decode_loop`` reports how the decode loops ran (graph captures / replays / eager).
 
-The JSON line also carries
+A plain run sets up, warms up, times the --steps passes, writes --dump-outputs if asked and prints the JSON line.
+``--dump-outputs DIR`` writes what the last timed pass returned to its caller (the WhisperResult: per segment and per word
+  times, probabilities and token ids) as float64 ``DIR/<name>.npy``, so that two builds can be compared output for output.
+With ``--full`` the JSON line also carries (each leg can still be left out with its --no-* switch)
   roofline     -- the dominant kernel class of an extra, instrumented pass (HIP events on the launch stream inside
                   libswx): algorithmic flops (or bytes) / measured time vs the gfx950 peak
   cpu_baseline -- the CPU oracle (oracle/, a port: the reference's CPU path is not runnable offline) on ONE window of the
@@ -102,6 +105,48 @@ def _pmc_traffic():
         return {}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(res, out_dir):
+    """The WhisperResult of the last timed pass as float64 arrays: per segment start / end / avg_logprob / no_speech_prob /
+    compression_ratio, per word start / end / probability and the index of its segment, and the token ids of segments and
+    words flattened, with a count array beside each (None -> NaN).  Above DUMP_LIMIT_BYTES every array keeps a fixed, seeded
+    sample of its entries and <name>_index.npy says which."""
+    segs = res.segments
+    words = [(i, w) for i, s in enumerate(segs) for w in (s.words or [])]
+
+    def num(v):
+        return np.nan if v is None else float(v)
+    arrays = {
+        "segment_start": [num(s.start) for s in segs],
+        "segment_end": [num(s.end) for s in segs],
+        "segment_avg_logprob": [num(s.avg_logprob) for s in segs],
+        "segment_no_speech_prob": [num(s.no_speech_prob) for s in segs],
+        "segment_compression_ratio": [num(s.compression_ratio) for s in segs],
+        "segment_token_count": [len(s.tokens) for s in segs],
+        "segment_tokens": [t for s in segs for t in s.tokens],
+        "word_segment": [i for i, _ in words],
+        "word_start": [num(w.start) for _, w in words],
+        "word_end": [num(w.end) for _, w in words],
+        "word_probability": [num(w.probability) for _, w in words],
+        "word_token_count": [len(w.tokens or []) for _, w in words],
+        "word_tokens": [t for _, w in words for t in (w.tokens or [])],
+    }
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:              # each sampled entry costs 8 bytes of value + 8 of index
+        keep = DUMP_LIMIT_BYTES / (2.0 * total)
+        rng = np.random.default_rng(0)
+        for k in list(arrays):
+            idx = np.sort(rng.choice(arrays[k].size, int(arrays[k].size * keep), replace=False))
+            arrays[k], arrays[k + "_index"] = arrays[k][idx], idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    log(f"outputs of the last timed step: {len(arrays)} arrays, {sum(a.nbytes for a in arrays.values())} bytes -> {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -139,15 +184,21 @@ def main():
                     "decode loop without the captured step graph")
     ap.add_argument("--ab-flags", type=int, default=0, help="A/B inside ONE process (GPU boxes differ by up to 40 %): after the timed "
                     "steps, three more passes each with and without these swx_debug_flags() bits, alternating; reported as `ab`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-f32", action="store_true", help="skip the strict-f32 leg")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the roofline pass, the strict-f32 "
+                    "leg and the CPU baseline (a plain run does none of them)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step returned as "
+                    "DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline pass")
+    ap.add_argument("--no-f32", action="store_true", help="--full: skip the strict-f32 leg")
     ap.add_argument("--host-profile", default="", help="diagnostic: one extra pass under cProfile, the 40 heaviest functions "
                     "(by own time) written to this file; not part of `value`")
     ap.add_argument("--phase-times", action="store_true", help="one extra pass with a device synchronise at every stage "
                     "boundary: wall ms per stage (host share of the pass) under \"phase_ms\"; not part of `value`")
     ap.add_argument("--cpu-budget", type=float, default=240.0, help="hard cap (s) on the CPU-baseline leg")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # Every N runs the SAME per-GPU workload -- BASELINE.json configs[2]: 10 min, 20 windows in one batch, per rank -- so that the
     # values at N = 1, 2, 4, 8 are one weak-scaling curve (per-GPU work fixed as N grows; rounds 3-5 switched N > 1 to 60 min at
     # 120 windows per batch, which made value(N) / (N x value(1)) compare two workloads).  One GPU's share of configs[4] (8 h over
@@ -262,6 +313,8 @@ def main():
                             device=dev if _dist.is_initialized() and _dist.get_backend() == "nccl" else None)
 
     log(f"timed region done: {dt:.3f}s for {args.steps} steps")
+    if rank == 0 and args.dump_outputs and res is not None:
+        dump_outputs(res, args.dump_outputs)
     ab = None
     if args.ab_flags and world == 1:
         lib_ = model.engine.lib
@@ -359,7 +412,7 @@ def main():
         out["phase_ms"] = ph
 
     # ---- roofline: one extra instrumented pass (not part of `value`)
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         log("instrumented pass (roofline)")
         lib = model.engine.lib
         lib.swx_prof_enable(1)
@@ -418,7 +471,7 @@ def main():
                          avg_launch_us=r["avg_us"], unit="TFLOP/s" if r["bound"] == "mfma" else "GB/s"))
 
     # ---- strict-parity mode (f32) on the same workload: one warm-up + three timed passes (median), rank 0 at N=1
-    if rank == 0 and world == 1 and not args.no_f32 and args.dtype != "f32":
+    if rank == 0 and world == 1 and args.full and not args.no_f32 and args.dtype != "f32":
         log("strict f32 leg")
         try:
             del model
@@ -445,7 +498,7 @@ def main():
         model = None
 
     # ---- CPU baseline (oracle port), bounded sample, rank 0 at N=1 only
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         log("cpu baseline (oracle port)")
         model = None
         torch.cuda.empty_cache()

@@ -2,7 +2,9 @@
 # usage: gpurun --timeout 2400 -- 'bash scripts/gpu_final.sh [tag]'
 # The round's measurement set: (1) HBM traffic counters per kernel class (separate FETCH_SIZE / WRITE_SIZE passes, kernel-trace
 # only) -> profiles/pmc_traffic.json (read by bench.py's roofline object), (2) rocprofv3 --kernel-trace --stats of the default
-# bench command, (3) the default bench line (with the strict-f32 leg and the CPU baseline), (4) smoke + the GPU test suite.
+# bench command, (3) the default bench line with --full (the roofline pass, the strict-f32 leg and the CPU baseline), written to
+# $OUT (default bench_out/), (4) smoke + the GPU test suite.
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"
 tag=${1:-final}
 mkdir -p gpurun_out
 export TMPDIR=/tmp
@@ -64,5 +66,5 @@ mkdir -p profiles && cp gpurun_out/pmc_traffic.json profiles/pmc_traffic.json   
 scripts/rocprof_kernels.sh bench_$tag python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-roofline --no-f32
 head -30 gpurun_out/bench_${tag}_kernels.csv
 echo "== smoke"; ( timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 )
-echo "== default bench line"; ( timeout 900 python bench.py 2>&1 | tail -1 ) | tee gpurun_out/bench_$tag.json | cut -c1-4000
+echo "== default bench line (--full)"; ( timeout 900 python bench.py --full 2>&1 | tail -1 ) | tee "$OUT/bench_$tag.json" | cut -c1-4000
 if [ -z "$SKIP_SUITE" ]; then echo "== gpu suite"; ( timeout 1500 python -m pytest tests -m gpu -q --timeout=900 2>&1 | tail -8 ) | tee gpurun_out/gpu_suite_$tag.log; fi

@@ -1,11 +1,12 @@
 #!/bin/bash
 # usage: gpurun -- 'bash scripts/gpu_suite.sh'
-# whole GPU suite, smoke, bench line, rocprofv3 kernel stats of the bench command
+# whole GPU suite, smoke, bench line (--full, written to $OUT, default bench_out/), rocprofv3 kernel stats of the bench command
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 ( timeout 60 python __graft_entry__.py smoke 2>&1 | tail -3 ) > gpurun_out/smoke.log
 ( timeout 900 python -m pytest tests -m gpu -q -n 4 --timeout=400 2>&1 | tail -8 ) > gpurun_out/gpu_tests.log
-( timeout 240 python bench.py 2> gpurun_out/bench.err | tail -2 ) > gpurun_out/bench.log
+( timeout 240 python bench.py --full 2> "$OUT/bench.err" | tail -2 ) > "$OUT/bench.log"
 cd /tmp && ( timeout 200 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/prof -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-roofline 2>&1 | tail -3 ) > $GRAFT_REPO_ROOT/gpurun_out/rocprof.log
 cd $GRAFT_REPO_ROOT
 python - <<'PY'
@@ -24,4 +25,4 @@ for db in glob.glob('gpurun_out/prof/*.db'):
             f.write('"%s",%d,%d,%d,%d,%.3f,%.3f\n' % (r[0][:60], r[1], r[2], r[3], r[4], r[5], r[6]))
 PY
 rm -f gpurun_out/prof/*.db
-cat gpurun_out/smoke.log; tail -5 gpurun_out/gpu_tests.log; tail -2 gpurun_out/bench.err; cut -c1-1800 gpurun_out/bench.log; head -14 gpurun_out/kernel_stats.csv
+tail -2 "$OUT/bench.err"; cut -c1-1800 "$OUT/bench.log"

@@ -8,6 +8,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 import torch
 import torch.multiprocessing as mp
@@ -15,7 +16,7 @@ import torch.multiprocessing as mp
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _rank(rank, world, port, q, mode):
+def _rank(rank, world, port, q, mode, dump):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
@@ -54,7 +55,7 @@ def _rank(rank, world, port, q, mode):
     torch.cuda.synchronize = lambda *_: None
     torch.cuda.empty_cache = lambda: None
     sys.argv = ["bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "1", "--model", "tiny.en", "--minutes", "1", "--batch", "2",
-                "--beam", "1", "--tokens", "6", "--host-audio", "--no-roofline", "--no-cpu-baseline", "--no-f32", "--mode", mode]
+                "--beam", "1", "--tokens", "6", "--host-audio", "--no-roofline", "--no-cpu-baseline", "--no-f32", "--mode", mode, "--dump-outputs", os.path.join(dump, f"rank{rank}")]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main()
@@ -62,11 +63,11 @@ def _rank(rank, world, port, q, mode):
 
 
 @pytest.mark.parametrize("mode", ["transcribe", "sharded"])
-def test_bench_two_ranks_dry_run(mode):
+def test_bench_two_ranks_dry_run(mode, tmp_path):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = 33500 + (os.getpid() % 2000) + (41 if mode == "sharded" else 0)
-    procs = [ctx.Process(target=_rank, args=(r, 2, port, q, mode)) for r in range(2)]
+    procs = [ctx.Process(target=_rank, args=(r, 2, port, q, mode, str(tmp_path))) for r in range(2)]
     for p in procs:
         p.start()
     got = sorted(q.get(timeout=240) for _ in range(2))
@@ -90,3 +91,13 @@ def test_bench_two_ranks_dry_run(mode):
         assert rec["config"]["windows_per_gpu"] == 4                # the gathered result covers the recording of both ranks
     assert arena0 and arena1                                        # the broadcast reached rank 1
     assert calls0 == dict(mark=0, load=1) and calls1 == dict(mark=1, load=0), (calls0, calls1)
+    # --dump-outputs: rank 0 writes what its last timed step returned, in float64; the other ranks write nothing
+    assert not (tmp_path / "rank1").exists()
+    dumped = {f.stem: np.load(f) for f in (tmp_path / "rank0").glob("*.npy")}
+    assert all(a.dtype == np.float64 for a in dumped.values()), {k: a.dtype for k, a in dumped.items()}
+    assert len(dumped["segment_start"]) == len(dumped["segment_end"]) == len(dumped["segment_token_count"]) >= 1
+    assert len(dumped["word_start"]) == len(dumped["word_probability"]) == len(dumped["word_segment"]) == rec["config"]["words"]
+    assert len(dumped["segment_start"]) == rec["config"]["segments"]
+    assert dumped["segment_token_count"].sum() == len(dumped["segment_tokens"])
+    assert dumped["word_token_count"].sum() == len(dumped["word_tokens"])
+    assert np.all(dumped["word_end"] >= dumped["word_start"])
