@@ -109,7 +109,7 @@ typedef struct swx_decode_cfg {
     float temperature;            /* 0 = argmax */
     float patience;               /* beam: max_candidates = round(G * patience); <=0 -> 1.0 */
     int32_t sample_len;           /* max sampled tokens (n_text_ctx/2 = 224 by default) */
-    int32_t sample_begin;         /* len(initial_tokens) (same for every window of a job) */
+    int32_t sample_begin;         /* len(initial_tokens) of every window (per window: sample_begins below) */
     int32_t sot_index;            /* index of <|startoftranscript|> in the initial tokens */
     int32_t suppress_blank;       /* SuppressBlank */
     int32_t apply_timestamp_rules;/* ApplyTimestampRules (0 when without_timestamps) */
@@ -134,16 +134,30 @@ typedef struct swx_decode_cfg {
                                      reference's decoding loop makes them -- the sampled tokens are the reference's for the
                                      same seed; the counter-based hash above is not used.  HBM cost: sample_len * W * G * n_vocab
                                      * 4 bytes (232 MB for large-v3 at sample_len 224, best_of 5), read once per step. */
+    const int32_t *sample_begins; /* HOST array [W] or NULL: len(initial_tokens) of every window -- a RAGGED job, e.g. the windows of
+                                     several recordings that each carry their own prompt.  NULL: every window has `sample_begin`
+                                     tokens (arrays whose entries all agree are that job too: the same launches, the same captured
+                                     graph).  With the array `sample_begin` is ignored and d_init_tokens is
+                                     [W][max_w sample_begins[w]], rows padded with `eot`.  Every window computes what it computes
+                                     as a job of its own: the step counter is shared (all windows sample their token i in the same
+                                     unit), positions, the timestamp rules' view of tokens[sample_begin:], lengths and the
+                                     context-full exit (decode.py:60: a window stops after sampling token
+                                     n_text_ctx - sample_begins[w] and is finalized as at a loop exit, the others go on) are per
+                                     window.  The job ends when every window is finished or context-full, or sample_len is used up.
+                                     Each entry in [1, n_text_ctx], else "invalid argument". */
+    const int32_t *sot_indices;   /* HOST array [W] or NULL (= `sot_index` for every window): index of <|startoftranscript|> in
+                                     every window's initial tokens, in [0, sample_begins[w]), else "invalid argument" */
 } swx_decode_cfg;
 
 /* runs the whole loop; outputs (device):
  *  d_tokens_out  int32 [W][G_out][n_ctx+1]   final sequences incl. the initial tokens, eot-padded
- *  d_lens_out    int32 [W][G_out]            length up to (excluding) the first eot after sample_begin
+ *  d_lens_out    int32 [W][G_out]            length up to (excluding) the first eot after the window's sample_begin
  *  d_sumlp_out   f32   [W][G_out]            sum_logprobs of each candidate
  *  d_nospeech    f32   [W]                   softmax(logits[sot_index])[no_speech] at step 0 (decode.py:42-44)
  *  G_out = G (greedy/best-of) or max(G, max_candidates) (beam)
- * inputs: d_init_tokens int32 [W][sample_begin]; d_suppress int32 [n_suppress];
+ * inputs: d_init_tokens int32 [W][sample_begin] ([W][longest window], eot-padded, with cfg->sample_begins); d_suppress int32 [n_suppress];
  *         d_ts_mask uint8 [W][1501] or NULL (decode.py:14-16,54); d_xkv from swx_cross_kv for these W windows.
+ * In a ragged job d_tokens_out[w] holds window w's own initial tokens followed by its samples (no padding in between).
  * Returns the number of steps executed (>=0) or a negative error.  Blocks until the loop has finished. */
 int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_tokens, const int32_t *d_suppress,
                const uint8_t *d_ts_mask, const void *d_xkv, int32_t *d_tokens_out, int32_t *d_lens_out,

@@ -11,6 +11,8 @@ struct DecodeBufs {
     int32_t *tokens[2];        // [M][TS] (double buffered for the beam gather)
     int32_t *anc[2];           // [M][n_ctx] ancestor tables (null when G == 1)
     int32_t *pos0;             // [M] position of the token the next forward pass embeds
+    const int32_t *begin;      // [W] initial tokens per window of a ragged job (n_init is then the longest: the row stride of the
+                               //     initial-token array and the bound the host plans with), or null: every window has n_init
     float *sum_lp, *sum_lp_next;   // [M]
     int32_t *row_done;         // [M]
     int32_t *win_done, *win_done_prev;   // [W]

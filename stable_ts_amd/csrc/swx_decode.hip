@@ -111,16 +111,22 @@ __device__ __forceinline__ float gumbel(uint64_t seed, unsigned row_uid, unsigne
     return -logf(-logf(u));
 }
 
+// Number of initial tokens of window w: the job's common value, or the window's own in a ragged job (DecodeBufs::begin).  The
+// step counter is common to all windows either way -- window w holds begin + step tokens when unit `step` selects.
+__device__ __forceinline__ int win_begin(const DecodeBufs &b, int w) { return b.begin ? b.begin[w] : b.n_init; }
+
 // ---------------------------------------------------------------------------------------------------- init
 __global__ void decode_init_kernel(DecodeBufs b, const int32_t *__restrict__ init_tokens)
 {
     // grid (M): tokens = [init | eot ...], pos0 = 0, sum_logprobs = 0, flags cleared
+    // (init_tokens rows are b.n_init apart: the common length, or the longest window's in a ragged job)
     const int r = blockIdx.x;
     const int w = r / b.G;
+    const int n0 = win_begin(b, w);
     int32_t *row0 = b.tokens[0] + (size_t)r * b.TS;
     int32_t *row1 = b.tokens[1] + (size_t)r * b.TS;
     for (int i = threadIdx.x; i < b.TS; i += blockDim.x) {
-        const int32_t t = (i < b.n_init) ? init_tokens[(size_t)w * b.n_init + i] : b.cfg.eot;
+        const int32_t t = (i < n0) ? init_tokens[(size_t)w * b.n_init + i] : b.cfg.eot;
         row0[i] = t;
         row1[i] = t;
     }
@@ -135,17 +141,18 @@ __global__ void decode_init_kernel(DecodeBufs b, const int32_t *__restrict__ ini
 
 __global__ void decode_after_prefill_kernel(DecodeBufs b)
 {
-    // grid (M): every row of window w reads the prefill K/V of physical row w*G; first new position = n_init
+    // grid (M): every row of window w reads the prefill K/V of physical row w*G; first new position = the window's n_init
     const int r = blockIdx.x;
     const int w = r / b.G;
+    const int n0 = win_begin(b, w);
     if (b.anc[0]) {
         for (int p = threadIdx.x; p < b.n_ctx; p += blockDim.x) {
-            const int v = (p < b.n_init) ? w * b.G : r;
+            const int v = (p < n0) ? w * b.G : r;
             b.anc[0][(size_t)r * b.n_ctx + p] = v;
             b.anc[1][(size_t)r * b.n_ctx + p] = v;
         }
     }
-    if (threadIdx.x == 0) b.pos0[r] = b.n_init - 1;   // the select kernel advances it to n_init when it appends
+    if (threadIdx.x == 0) b.pos0[r] = n0 - 1;         // the select kernel advances it to n_init when it appends
 }
 
 // replicate the W prefill logits rows to the M sequence rows; no-speech probability from the SOT-position logits
@@ -183,8 +190,9 @@ __global__ __launch_bounds__(SEL_T) void decode_select_kernel(DecodeBufs b, int 
     if (b.win_done[w]) return;    // frozen: upstream stopped iterating for this audio
     float *lg = b.logits + (size_t)r * V;
     int32_t *tok = b.tokens[cur] + (size_t)r * b.TS;
-    const int len = b.n_init + step;            // tokens so far
-    const int nsamp = len - c.sample_begin;     // sampled so far
+    const int n0 = win_begin(b, w);
+    const int len = n0 + step;                  // tokens so far
+    const int nsamp = step;                     // sampled so far (the same for every window of the job)
     const int tsb = c.timestamp_begin;
 
     // ---- SuppressBlank / SuppressTokens / min_tokens
@@ -199,7 +207,7 @@ __global__ __launch_bounds__(SEL_T) void decode_select_kernel(DecodeBufs b, int 
         __syncthreads();
         // last timestamp token among the sampled tokens (they never decrease, but take the LAST occurrence as upstream)
         int my = -1;
-        for (int i = c.sample_begin + tid; i < len; i += SEL_T) if (tok[i] >= tsb) my = i;
+        for (int i = n0 + tid; i < len; i += SEL_T) if (tok[i] >= tsb) my = i;
         if (my >= 0) atomicMax(&sh_last_ts, my);
         __syncthreads();
         const int last_ts_pos = sh_last_ts;
@@ -277,7 +285,10 @@ __global__ __launch_bounds__(SEL_T) void decode_select_kernel(DecodeBufs b, int 
             const float lp = (lg[next] - mx) - lse;
             if (!prev_eot) b.sum_lp[r] += lp; else next = c.eot;
             tok[len] = next;
-            b.pos0[r] = len;                      // position of the token the next forward pass embeds
+            // position of the token the next forward pass embeds.  len == n_ctx: the window's context is full and it is frozen
+            // from here on (decode_step_finish_kernel); the passes of the other windows' later steps still run over its rows
+            // and must stay inside the positional table and the K/V cache
+            if (len < b.n_ctx) b.pos0[r] = len;
             b.row_done[r] = (next == c.eot) ? 1 : 0;
         }
     } else {
@@ -319,8 +330,9 @@ __global__ __launch_bounds__(SEL_T) void decode_select_reg_kernel(DecodeBufs b, 
     if (b.win_done[w]) return;
     float *lg = b.logits + (size_t)r * V;
     int32_t *tok = b.tokens[cur] + (size_t)r * b.TS;
-    const int len = b.n_init + step;
-    const int nsamp = len - c.sample_begin;
+    const int n0 = win_begin(b, w);
+    const int len = n0 + step;
+    const int nsamp = step;
     const int tsb = c.timestamp_begin;
 
     if (c.suppress_blank && nsamp == 0 && tid == 0) { if (c.blank_token >= 0) lg[c.blank_token] = NEG_INF; lg[c.eot] = NEG_INF; }
@@ -335,7 +347,7 @@ __global__ __launch_bounds__(SEL_T) void decode_select_reg_kernel(DecodeBufs b, 
 
     if (c.apply_timestamp_rules) {
         int my = -1;
-        for (int i = c.sample_begin + tid; i < len; i += SEL_T) if (tok[i] >= tsb) my = i;
+        for (int i = n0 + tid; i < len; i += SEL_T) if (tok[i] >= tsb) my = i;
         if (my >= 0) atomicMax(&sh_last_ts, my);
         __syncthreads();
         const int last_ts_pos = sh_last_ts;
@@ -434,7 +446,7 @@ __global__ __launch_bounds__(SEL_T) void decode_select_reg_kernel(DecodeBufs b, 
             const float lp = (sh_raw - mx) - lse;
             if (!prev_eot) b.sum_lp[r] += lp; else next = c.eot;
             tok[len] = next;
-            b.pos0[r] = len;
+            if (len < b.n_ctx) b.pos0[r] = len;
             b.row_done[r] = (next == c.eot) ? 1 : 0;
         }
     } else {
@@ -486,7 +498,7 @@ __global__ __launch_bounds__(256) void decode_beam_update_kernel(DecodeBufs b, i
     if (tid == 0) s_frozen = b.win_done[w];
     __syncthreads();
     const bool frozen = s_frozen != 0;            // upstream stopped iterating for this audio: carry its state over
-    const int len = b.n_init + step;
+    const int len = win_begin(b, w) + step;
     const int nb = (step == 0) ? 1 : G;           // at the first step every beam is the same sequence: the
                                                   // upstream dict of candidate sequences collapses to beam 0's
     const int nc = nb * K;
@@ -560,17 +572,19 @@ __global__ __launch_bounds__(256) void decode_beam_update_kernel(DecodeBufs b, i
             for (int p = tid; p < b.n_ctx; p += 256) da[p] = (p < len) ? sa[p] : dst;
             // (sum_logprobs written in place: every read of this window's rows sits in front of the barriers above and no other
             //  workgroup touches them -- the separate commit launch of rounds 1-5 cost 4.7 us per step)
-            if (tid == 0) { b.sum_lp[dst] = sel_sc[s]; b.pos0[dst] = len; }
+            if (tid == 0) { b.sum_lp[dst] = sel_sc[s]; if (len < b.n_ctx) b.pos0[dst] = len; }   // (len == n_ctx: see the selection)
         }
     }
 }
 
-// per-window completion (greedy: every row ended with EOT) and the global "all done" counter
+// per-window completion (greedy: every row ended with EOT; ragged job: the window's context is full) and the global "all done"
+// counter
 __global__ __launch_bounds__(64) void decode_step_finish_kernel(DecodeBufs b)
 {
     // one wave, a window per lane (one lane had walked the windows one dependent load after the other: 6 us per step at 20 windows)
     if (blockIdx.x != 0) return;
     const int lane = threadIdx.x;
+    const int step = *b.step_dev;                 // index of the token this unit selected
     int nd = 0;
     for (int w = lane; w < b.W; w += 64) {
         int done = b.win_done[w];
@@ -579,12 +593,16 @@ __global__ __launch_bounds__(64) void decode_step_finish_kernel(DecodeBufs b)
             for (int g = 0; g < b.G; ++g) all &= b.row_done[w * b.G + g];
             if (all) { b.win_done[w] = 1; done = 1; }
         }
+        // tokens.shape[-1] > n_ctx (decode.py:60) for THIS window: upstream, where every window is its own job, leaves the loop
+        // here; the window is frozen like a finished one and finalized as a loop exit while the others go on.  (A job with one
+        // common length ends on the host at this step: swx_decode)
+        if (b.begin && !done && b.begin[w] + step + 1 > b.n_ctx) { b.win_done[w] = 1; done = 1; }
         b.win_done_prev[w] = done;
         nd += done ? 1 : 0;
     }
     nd += lane_xor<32>(nd, lane); nd += lane_xor<16>(nd, lane); nd += lane_xor<8>(nd, lane);
     nd += lane_xor<4>(nd, lane); nd += lane_xor<2>(nd, lane); nd += lane_xor<1>(nd, lane);
-    if (lane == 0) { *b.n_done = nd; *b.step_dev += 1; }
+    if (lane == 0) { *b.n_done = nd; *b.step_dev = step + 1; }
 }
 
 // ------------------------------------------------------------------------------------------------ finalize
@@ -640,7 +658,7 @@ __global__ void decode_finalize_kernel(DecodeBufs b, int cur, int n_steps, int32
         }
     }
     __syncthreads();
-    // lens: tokens[sample_begin : first eot]; unused candidate slots get len = -1
+    // lens: tokens[the window's sample_begin : first eot]; unused candidate slots get len = -1
     for (int k = tid; k < G_out; k += blockDim.x) {
         if (k >= n_out) { lens_out[(size_t)w * G_out + k] = -1; continue; }
     }
@@ -648,9 +666,10 @@ __global__ void decode_finalize_kernel(DecodeBufs b, int cur, int n_steps, int32
     if (tid == 0) {
         for (int k = 0; k < n_out; ++k) {
             const int32_t *dt = tokens_out + ((size_t)w * G_out + k) * TS;
-            int e = c.sample_begin;
+            const int n0 = win_begin(b, w);
+            int e = n0;
             while (e < TS && dt[e] != c.eot) ++e;
-            lens_out[(size_t)w * G_out + k] = e - c.sample_begin;
+            lens_out[(size_t)w * G_out + k] = e - n0;
         }
     }
 }

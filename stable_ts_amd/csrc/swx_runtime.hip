@@ -1,6 +1,7 @@
 // swx_runtime.hip -- the C ABI of libswx.so (include/swx.h): weight arena, workspace, and the host-side drivers that
 // sequence the gfx950 kernels for the encoder, the decoding loop and the teacher-forced scoring pass.
 // No device allocation happens here: the caller binds the arena and the workspace (PyTorch owns the memory).
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <string>
@@ -67,7 +68,7 @@ struct swx_model {
     int max_windows = 0, max_rows = 0, ws_n_align = 0;
     struct WsLayout {
         size_t melT, h1, x, h, qkv, att, u, gmax, small_i32, zeros_i32, ticket;
-        size_t tokens0, tokens1, anc0, anc1, pos0, sum_lp, sum_lp_next, row_done, win_done, win_done_prev, n_done;
+        size_t tokens0, tokens1, anc0, anc1, pos0, win_begin, sum_lp, sum_lp_next, row_done, win_done, win_done_prev, n_done;
         size_t fin_tokens, fin_score, fin_len, fin_count, cand_lp, cand_tok, logits, hid2;
         size_t kcache, vcache, sk, sv, cap, mean, sd, suppress, slabs, heads, win_uid;
         size_t total;
@@ -82,6 +83,8 @@ struct swx_model {
     struct StepGraph { std::vector<uint64_t> key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; uint64_t used = 0; };
     std::vector<StepGraph> graphs;
     uint64_t graph_clock = 0;
+    std::vector<int32_t> ragged_hv;       // host side of a ragged decode job's per-window arrays: lives on the handle so that the
+                                          // upload needs no host wait (swx_decode returns only when its stream has drained)
     hipStream_t cap_stream = nullptr;   // capture happens here (the caller's stream may be the null stream, which cannot capture)
     bool graphs_off = false;            // set when capture / replay failed in three swx_decode calls of this handle: eager from then on
     int graph_failures = 0;
@@ -248,6 +251,7 @@ void ws_layout(const swx_model *m, int Bmax, int Mmax, int n_align, swx_model::W
     L.anc0 = take((size_t)Mmax * D.n_text_ctx * 4);
     L.anc1 = take((size_t)Mmax * D.n_text_ctx * 4);
     L.pos0 = take((size_t)Mmax * 4);
+    L.win_begin = take((size_t)Bmax * 4 * 3);      // ragged decode job: [W] initial lengths | [2W] prefill rows of the final LayerNorms
     L.sum_lp = take((size_t)Mmax * 4);
     L.sum_lp_next = take((size_t)Mmax * 4);
     L.row_done = take((size_t)Mmax * 4);
@@ -350,6 +354,8 @@ struct FwdCfg {
     int row_mul;           // logical row id = grid row * row_mul
     int n_new;             // new tokens per row
     const int32_t *tokens; int64_t ld_tok;
+    int xkv_W;             // windows in the cross-K/V buffer `xkv` was cut from (its layer stride); 0 = W.  A pass over windows
+                           // [w0, w0 + W) of a larger job points xkv at window w0's chunk of layer 0
     const int32_t *pos0;   // device, indexed by logical row id
     unsigned char *kcache, *vcache;
     size_t layer_stride;   // bytes between layers in the cache (0 = single-layer scratch)
@@ -423,7 +429,7 @@ int decoder_step_dec(swx_model *m, const FwdCfg &f, hipStream_t s)
             g.pf = pf_of(w.wco_p, d, d, DEC_RES);                // used after the cross-attention (154 MB through the cache)
             SWX_TRY(swx_gemm_dec(g, s));
         }
-        const unsigned char *kl = f.xkv + (size_t)l * f.W * chunk * e;
+        const unsigned char *kl = f.xkv + (size_t)l * (f.xkv_W ? f.xkv_W : f.W) * chunk * e;
         AttnArgs ca{};
         ca.q = q; ca.ldq = d; ca.k = kl; ca.v = kl + (size_t)D.n_audio_ctx * d * e; ca.ldkv = d;
         ca.k_bs = chunk; ca.v_bs = chunk; ca.vt_kp = SWX_VT_KP; ca.o = att; ca.ldo = d;
@@ -504,7 +510,7 @@ int decoder_forward_dec(swx_model *m, const FwdCfg &f, hipStream_t s)
             hipError_t qe = hipMemcpyAsync(f.qcap + (size_t)l * rows * d * e, q, (size_t)rows * d * e, hipMemcpyDeviceToDevice, s);
             if (qe != hipSuccess) return -100 - (int)qe;
         }
-        const unsigned char *kl = f.xkv + (size_t)l * f.W * chunk * e;
+        const unsigned char *kl = f.xkv + (size_t)l * (f.xkv_W ? f.xkv_W : f.W) * chunk * e;
         AttnArgs ca{};
         ca.q = q; ca.ldq = d; ca.k = kl; ca.v = kl + (size_t)D.n_audio_ctx * d * e; ca.ldkv = d;
         ca.k_bs = chunk; ca.v_bs = chunk; ca.vt_kp = SWX_VT_KP; ca.o = att; ca.ldo = d;
@@ -582,7 +588,7 @@ int decoder_forward(swx_model *m, const FwdCfg &f, hipStream_t s)
         }
         // cross K/V of this layer: per window [K: 1500 x d row-major | V^T: d x SWX_VT_KP, keys contiguous]
         const int64_t chunk = xkv_chunk_elems(m);
-        const unsigned char *kl = f.xkv + (size_t)l * f.W * chunk * e;
+        const unsigned char *kl = f.xkv + (size_t)l * (f.xkv_W ? f.xkv_W : f.W) * chunk * e;
         AttnArgs ca{};
         ca.q = qkv; ca.ldq = d; ca.k = kl; ca.v = kl + (size_t)D.n_audio_ctx * d * e; ca.ldkv = d;
         ca.k_bs = chunk; ca.v_bs = chunk; ca.vt_kp = SWX_VT_KP; ca.o = att; ca.ldo = d;
@@ -626,7 +632,7 @@ swx_model::StepGraph *step_graph(swx_model *m, const DecodeBufs &b, const void *
         (uint64_t)(int64_t)c.blank_token, (uint64_t)c.n_suppress, (uint64_t)c.min_tokens, (uint64_t)c.seed,
         (uint64_t)(uintptr_t)b.ts_mask, (uint64_t)(uintptr_t)b.win_uid, (uint64_t)(uintptr_t)d_xkv, (uint64_t)(uintptr_t)m->arena,
         (uint64_t)(uintptr_t)m->ws, (uint64_t)m->ws_bytes, (uint64_t)g_debug_flags, (uint64_t)cur, (uint64_t)m->is_folded(),
-        (uint64_t)(uintptr_t)c.noise};
+        (uint64_t)(uintptr_t)c.noise, (uint64_t)(uintptr_t)b.begin};
     ++m->graph_clock;
     for (auto &g : m->graphs) if (g.key == key) { g.used = m->graph_clock; return &g; }
     if (!m->cap_stream && hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking) != hipSuccess) { m->cap_stream = nullptr; return nullptr; }
@@ -1143,6 +1149,18 @@ int swx_cross_kv(swx_model *m, const void *d_xa, int B, void *d_xkv, void *strea
 }
 
 // ----------------------------------------------------------------------------------------------------- decode
+namespace {
+// row idx[j] of src -> row j of dst, row_bytes (a multiple of 16) each; grid (n)
+__global__ __launch_bounds__(64) void gather_rows_kernel(const unsigned char *__restrict__ src, const int32_t *__restrict__ idx,
+                                                         unsigned char *__restrict__ dst, int row_bytes)
+{
+    const int j = blockIdx.x;
+    const uint4 *sp = (const uint4 *)(src + (size_t)idx[j] * row_bytes);
+    uint4 *dp = (uint4 *)(dst + (size_t)j * row_bytes);
+    for (int i = threadIdx.x; i < row_bytes / 16; i += 64) dp[i] = sp[i];
+}
+}  // namespace
+
 int swx_decode_gout(const swx_decode_cfg *cfg)
 {
     if (!cfg) return 0;
@@ -1163,14 +1181,32 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
     if (W <= 0 || G <= 0 || G > MAX_GROUP) return -1;
     if (W > m->max_windows || M > m->max_rows) return -8;
     if (cfg->n_suppress > MAX_SUPPRESS || cfg->n_suppress < 0) return -2;
-    const int n_init = cfg->sample_begin;
-    if (n_init <= 0 || n_init > D.n_text_ctx) return -1;
+    // Initial tokens per window (swx.h: sample_begins / sot_indices).  Arrays whose entries all agree ARE the job with one common
+    // length: n_init / sot_index take the common value and every line below is the uniform job's.  Otherwise the job is ragged:
+    // nb[w] / si[w] per window, n_init = the longest (row stride of d_init_tokens, bound of the positions), n_min = the shortest.
+    int n_init = cfg->sample_begin, sot_index = cfg->sot_index;
+    std::vector<int32_t> nb, si;
+    if (cfg->sample_begins || cfg->sot_indices) {
+        nb.resize(W); si.resize(W);
+        for (int w = 0; w < W; ++w) {
+            nb[w] = cfg->sample_begins ? cfg->sample_begins[w] : cfg->sample_begin;
+            si[w] = cfg->sot_indices ? cfg->sot_indices[w] : cfg->sot_index;
+            if (nb[w] <= 0 || nb[w] > D.n_text_ctx || si[w] < 0 || si[w] >= nb[w]) return -1;
+        }
+        n_init = *std::max_element(nb.begin(), nb.end());
+        sot_index = si[0];
+    }
+    const int n_min = nb.empty() ? n_init : *std::min_element(nb.begin(), nb.end());
+    const bool ragged = !nb.empty() && (n_min != n_init || *std::min_element(si.begin(), si.end()) != *std::max_element(si.begin(), si.end()));
+    if (n_init <= 0 || n_init > D.n_text_ctx || sot_index < 0 || sot_index >= n_init) return -1;
     hipStream_t s = S(stream);
     const int d = D.n_text_state;
     const size_t e = m->esz;
 
     DecodeBufs b{};
     b.cfg = *cfg;
+    b.cfg.sample_begin = n_init; b.cfg.sot_index = sot_index;
+    b.cfg.sample_begins = nullptr; b.cfg.sot_indices = nullptr;      // host pointers: the kernels read b.begin
     if (cfg->beam || cfg->temperature == 0.f) b.cfg.noise = nullptr;      // only the sampling decoder draws
     b.W = W; b.G = G; b.M = M; b.V = D.n_vocab; b.TS = D.n_text_ctx + 1; b.n_ctx = D.n_text_ctx; b.n_init = n_init;
     const float pat = cfg->patience > 0.f ? cfg->patience : 1.0f;
@@ -1210,6 +1246,41 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
         b.win_uid = d_uid;
     }
     b.cfg.window_uid = nullptr;          // a host pointer: the kernels read the device copy (b.win_uid) only
+    // ragged job: the prefill is made over RUNS of neighbouring windows of one KIND, padded to the run's longest window.  The kind
+    // is what the pass's kernel choice depends on, so that a window is computed by the kernels it gets alone: one initial token
+    // (decoder_forward takes the single-token pass), 2-16 (the cross-attention's <= 16-query kernel, which splits the KEYS over
+    // its waves: another summation order than the query-block kernel), more than 16.  Every other kernel of the pass computes a
+    // row the same way whatever the launch (tests/test_gpu_batch_invariance.py).  One more choice does follow the PADDED length:
+    // swx_self_attention takes self_attn_cached below 8 new tokens, self_attn_cached_mq_f16<4> for 8-31, <8> from 32 on -- a window
+    // of 5 tokens next to one of 12 runs another self-attention kernel than alone.  Those three are bit-identical by construction
+    // (one arithmetic order, swx_attn.hip) and that is RELIED upon here; tests/test_gpu_ragged_decode.py has neighbours on both
+    // sides of 8 and of 32.  Rows past a window's own length are computed
+    // and never read: causal attention keeps them out of the real rows, and their K/V slots are overwritten by the window's
+    // first sampled tokens before a step attends to them.
+    auto kind = [](int n) { return n == 1 ? 0 : n <= 16 ? 1 : 2; };
+    struct Run { int w0, w1, n_new; };
+    std::vector<Run> runs;
+    int32_t *d_pre_rows = nullptr;
+    if (ragged) {
+        std::vector<int32_t> &hv = m->ragged_hv;         // [W] lengths | [2W] rows of a run's residual stream for the final LayerNorms
+        hv.assign(3 * (size_t)W, 0);
+        for (int w0 = 0; w0 < W; ) {
+            int w1 = w0 + 1, n_new = nb[w0];
+            while (w1 < W && kind(nb[w1]) == kind(nb[w0])) { n_new = std::max(n_new, (int)nb[w1]); ++w1; }
+            runs.push_back({w0, w1, n_new});
+            for (int w = w0; w < w1; ++w) {
+                hv[w] = nb[w];
+                hv[W + 2 * w] = (w - w0) * n_new + si[w];
+                hv[W + 2 * w + 1] = (w - w0) * n_new + nb[w] - 1;
+            }
+            w0 = w1;
+        }
+        int32_t *d_begin = m->Wp<int32_t>(m->L.win_begin);
+        hipError_t eb = hipMemcpyAsync(d_begin, hv.data(), hv.size() * 4, hipMemcpyHostToDevice, s);
+        if (eb != hipSuccess) return -100 - (int)eb;
+        b.begin = d_begin;
+        d_pre_rows = d_begin + W;
+    }
     hipError_t er = hipMemsetAsync(b.win_done_prev, 0, (size_t)W * 4, s);
     if (er != hipSuccess) return -100 - (int)er;
 
@@ -1229,15 +1300,34 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
     f.pos0 = m->Wp<int32_t>(m->L.zeros_i32);      // all zeros (any stride)
     f.kcache = m->ws + m->L.kcache; f.vcache = m->ws + m->L.vcache; f.layer_stride = layer_stride; f.cache_rows = m->max_rows;
     f.anc = nullptr; f.xkv = (const unsigned char *)d_xkv; f.capture = false;
-    SWX_TRY(decoder_forward(m, f, s));
     unsigned char *x = m->ws + m->L.x, *hid2 = m->ws + m->L.hid2;
-    // final LN of the rows at sot_index and at the last initial position of every window -> [W][2][d]
-    SWX_TRY(swx_layernorm(m->dtype, x + (size_t)cfg->sot_index * d * e, (int64_t)n_init * d, m->A<float>(m->o_ln_g),
-                          m->A<float>(m->o_ln_b), hid2, 2 * d, W, d, s));
-    SWX_TRY(swx_layernorm(m->dtype, x + (size_t)(n_init - 1) * d * e, (int64_t)n_init * d, m->A<float>(m->o_ln_g),
-                          m->A<float>(m->o_ln_b), hid2 + (size_t)d * e, 2 * d, W, d, s));
     // the prefill logits live at the tail of the logits region so that replication to rows [0, M) never overlaps
     float *lg2 = b.logits + (size_t)(m->L.logits_rows - 2 * W) * D.n_vocab;
+    if (!ragged) {
+        SWX_TRY(decoder_forward(m, f, s));
+        // final LN of the rows at sot_index and at the last initial position of every window -> [W][2][d]
+        SWX_TRY(swx_layernorm(m->dtype, x + (size_t)sot_index * d * e, (int64_t)n_init * d, m->A<float>(m->o_ln_g),
+                              m->A<float>(m->o_ln_b), hid2, 2 * d, W, d, s));
+        SWX_TRY(swx_layernorm(m->dtype, x + (size_t)(n_init - 1) * d * e, (int64_t)n_init * d, m->A<float>(m->o_ln_g),
+                              m->A<float>(m->o_ln_b), hid2 + (size_t)d * e, 2 * d, W, d, s));
+    } else {
+        // every run overwrites the residual stream: its two rows per window are parked (raw copies) where the prefill logits
+        // will land, and the final LN runs once over all 2W of them
+        unsigned char *park = (unsigned char *)(((uintptr_t)lg2 + 255) & ~(uintptr_t)255);      // (2W d-wide rows in 2W n_vocab-wide ones)
+        const size_t win_xkv = (size_t)xkv_chunk_elems(m) * e, win_cache = (size_t)G * D.n_text_ctx * d * e;
+        for (const Run &r : runs) {
+            FwdCfg fr = f;
+            fr.W = r.w1 - r.w0; fr.n_new = r.n_new; fr.xkv_W = W;
+            fr.tokens = f.tokens + (size_t)r.w0 * f.ld_tok;
+            fr.kcache = f.kcache + r.w0 * win_cache; fr.vcache = f.vcache + r.w0 * win_cache;
+            fr.xkv = f.xkv + r.w0 * win_xkv;
+            SWX_TRY(decoder_forward(m, fr, s));
+            hipLaunchKernelGGL(gather_rows_kernel, dim3(2 * fr.W), dim3(64), 0, s, x, d_pre_rows + 2 * r.w0,
+                               park + (size_t)2 * r.w0 * d * e, (int)(d * e));
+            SWX_CHECK_LAUNCH();
+        }
+        SWX_TRY(swx_layernorm(m->dtype, park, d, m->A<float>(m->o_ln_g), m->A<float>(m->o_ln_b), hid2, d, 2 * W, d, s));
+    }
     SWX_TRY(logits_gemm(m, hid2, d, 2 * W, lg2, s));
     SWX_TRY(swx_decode_after_prefill(b, lg2, d_nospeech, s));
 
@@ -1256,7 +1346,11 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
         // profiler's byte count only (steps = tokens sampled so far).  Never a captured kernel argument: a replayed graph would
         // carry the position of the step it was captured at (the profiler is off under replay, and 0 = "unknown" there)
         g.step_pos = capturing ? 0 : n_init + steps;
-        g.pos_bound = n_init + cfg->sample_len;        // (a property of the job, not of the step: safe to bake into the graph)
+        // a property of the job, not of the step: safe to bake into the graph.  Ragged job: the LONGEST window's bound, so a short
+        // window that alone takes self_attn_step_f16<false> (bound <= 128) takes the <true> / deep variant here: the step kernel of
+        // a row then depends on the job.  The variants differ only in code for positions >= 128 that such a row never reaches and
+        // are bit-identical below (swx_attn.hip); that identity is RELIED upon (tests/test_gpu_ragged_decode.py: 1 next to 228)
+        g.pos_bound = n_init + cfg->sample_len;
         const int fr = decoder_forward(m, g, st);
         if (fr < 0) return fr;
         unsigned char *hh = m->ws + m->L.h;
@@ -1268,7 +1362,9 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
     // returns 1 when the loop ends after the selection of token i
     auto after_select = [&](int i) -> int {
         steps = i + 1;
-        if (n_init + i + 1 > D.n_text_ctx) return 1;          // tokens.shape[-1] > n_ctx (decode.py:60)
+        // tokens.shape[-1] > n_ctx (decode.py:60).  Ragged job: a longer window met this earlier and was frozen on the device
+        // (decode_step_finish_kernel); the job ends when the shortest window meets it
+        if (n_min + i + 1 > D.n_text_ctx) return 1;
         // early-exit poll (one host sync); pointless while EOT is still suppressed by min_tokens
         if ((steps % CHECK == 0 && steps >= cfg->min_tokens) || steps == cfg->sample_len) {
             er = hipMemcpyAsync(&h_done, b.n_done, 4, hipMemcpyDeviceToHost, s);
@@ -1291,7 +1387,7 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
     swx_model::StepGraph *sg = nullptr;
     bool graph_failed_now = false;
     for (int i = 1; !stop; ) {
-        const bool pair = graph_ok && !m->graphs_off && !graph_failed_now && i >= 2 && (i & 1) == 0 && i + 1 < cfg->sample_len && n_init + i + 1 <= D.n_text_ctx;
+        const bool pair = graph_ok && !m->graphs_off && !graph_failed_now && i >= 2 && (i & 1) == 0 && i + 1 < cfg->sample_len && n_min + i + 1 <= D.n_text_ctx;
         if (pair) {
             if (!sg) sg = step_graph(m, b, d_xkv, cur, [&](hipStream_t cs) -> int {
                 SWX_TRY(unit(cur, cs, true));

@@ -16,6 +16,15 @@ from .audio import CHUNK_LENGTH
 from .tokenizer import Tokenizer, get_tokenizer
 
 
+# Windows whose initial tokens differ in length (per-window prompts) go to the engine as ONE lockstep job when it can run them
+# (Engine.ragged_decode).  False forces one job per distinct initial length, the only way there was before: for A/B runs.
+RAGGED_DECODE = True
+
+
+def use_ragged(model) -> bool:
+    return RAGGED_DECODE and bool(getattr(model.engine, "ragged_decode", False))
+
+
 def compression_ratio(text: str) -> float:
     raw = text.encode("utf-8")
     return len(raw) / len(zlib.compress(raw))
@@ -129,9 +138,11 @@ class DecodingPlan:
     def results(self, out: dict, audio_features: Sequence, languages: Sequence[str]) -> List[DecodingResult]:
         """upstream DecodingTask.run tail: cut at EOT, rank the group, decode text, statistics."""
         tok, o = self.tokenizer, self.options
-        sb = out["sample_begin"]
+        W = out["tokens"].shape[0]
+        begins = np.broadcast_to(np.asarray(out["sample_begin"]), (W,))      # an int, or one per window of a ragged job
         res = []
-        for w in range(out["tokens"].shape[0]):
+        for w in range(W):
+            sb = int(begins[w])
             cands, slps = [], []
             for k in range(out["tokens"].shape[1]):
                 ln = int(out["lens"][w, k])
@@ -157,8 +168,9 @@ class DecodingPlan:
 
 def decode_windows(model, xkv, options: DecodingOptions, ts_token_mask=None, prompts: Optional[Sequence[Sequence[int]]] = None,
                    audio_features=None) -> List[DecodingResult]:
-    """Decode W windows (the batch inside `xkv`) in lockstep.  `prompts` optionally gives per-window prompt token lists;
-    windows whose initial-token length differs are decoded in separate jobs (each job is one lockstep batch)."""
+    """Decode W windows (the batch inside `xkv`) in lockstep.  `prompts` optionally gives per-window prompt token lists.
+    Windows whose initial tokens differ in length are still one lockstep job on an engine that advertises `ragged_decode`;
+    on any other engine (or with `RAGGED_DECODE = False`) they are decoded as one job per distinct initial length."""
     W = xkv.n_windows
     if prompts is None:
         prompts = [options.prompt] * W
@@ -166,16 +178,25 @@ def decode_windows(model, xkv, options: DecodingOptions, ts_token_mask=None, pro
     if options.language is None and model.is_multilingual:
         raise ValueError("language must be resolved (detect_language) before decode_windows")
     languages = [options.language or "en"] * W
-    out_all = [None] * W
     if audio_features is None:
         audio_features = [None] * W
-    # group windows by initial length; windows of one group must be contiguous in xkv -> run per window otherwise
-    same = len({p.sample_begin for p in plans}) == 1
-    if same:
-        masks = None
-        if ts_token_mask is not None:
-            masks = ts_token_mask if ts_token_mask.ndim == 2 else ts_token_mask[None].expand(W, -1)
-        out = model.engine.decode(xkv, [list(p.initial_tokens) for p in plans], ts_mask=masks, **plans[0].engine_kwargs())
+    masks = None
+    if ts_token_mask is not None:
+        masks = ts_token_mask if ts_token_mask.ndim == 2 else ts_token_mask[None].expand(W, -1)
+    groups = {}
+    for w, p in enumerate(plans):
+        groups.setdefault((p.sample_begin, p.sot_index), []).append(w)
+    if len(groups) == 1 or use_ragged(model):
+        kw = plans[0].engine_kwargs()
+        if len(groups) > 1:
+            kw["sot_index"] = [p.sot_index for p in plans]
+        out = model.engine.decode(xkv, [list(p.initial_tokens) for p in plans], ts_mask=masks, **kw)
         return plans[0].results(out, audio_features, languages)
-    raise NotImplementedError("windows with different prompt lengths must be decoded as separate jobs "
-                              "(use model.engine.cross_kv per window)")
+    from . import transcribe as _t          # (the cross-K/V gather lives with the batch drivers)
+    res: List[Optional[DecodingResult]] = [None] * W
+    for ws in groups.values():
+        out = model.engine.decode(_t._xkv_select(model, xkv, ws), [list(plans[w].initial_tokens) for w in ws],
+                                  ts_mask=None if masks is None else masks[ws], **plans[ws[0]].engine_kwargs())
+        for w, r in zip(ws, plans[ws[0]].results(out, [audio_features[w] for w in ws], [languages[w] for w in ws])):
+            res[w] = r
+    return res

@@ -5,7 +5,7 @@ path is a libswx call.  Nothing here falls back to torch ops or to the CPU.
 """
 import ctypes
 from dataclasses import dataclass
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -47,6 +47,10 @@ def _i32arr(vals: Sequence[int]):
 
 
 class Engine:
+    # decode() takes windows whose initial tokens differ in length as one lockstep job (swx_decode_cfg.sample_begins); the batch
+    # drivers look for this attribute before they send such a job (decoding.use_ragged)
+    ragged_decode = True
+
     def __init__(self, dims: ModelDimensions, dtype: str = "f16", device: str = "cuda:0",
                  max_windows: int = 1, max_rows: int = 5, alignment_heads: Optional[Sequence[Tuple[int, int]]] = None):
         _lib.require_gpu()
@@ -227,8 +231,8 @@ class Engine:
 
     # ------------------------------------------------------------------ a3/a4 decode
     def decode(self, xkv: torch.Tensor, init_tokens: Sequence[Sequence[int]], *, n_group: int = 1, beam: bool = False,
-               temperature: float = 0.0, patience: Optional[float] = None, sample_len: int = 224, sot_index: int = 0,
-               suppress_blank: bool = True, apply_timestamp_rules: bool = True,
+               temperature: float = 0.0, patience: Optional[float] = None, sample_len: int = 224,
+               sot_index: Union[int, Sequence[int]] = 0, suppress_blank: bool = True, apply_timestamp_rules: bool = True,
                max_initial_timestamp_index: Optional[int] = None, eot: int = 0, sot: int = 0, no_timestamps: int = -1,
                timestamp_begin: int = 0, no_speech: int = -1, blank_token: int = -1,
                suppress_tokens: Sequence[int] = (), ts_mask: Optional[torch.Tensor] = None, min_tokens: int = 0,
@@ -239,10 +243,18 @@ class Engine:
         variates of every possible step are drawn up front (the same calls, so the same numbers), the device loop reads
         them (``swx_decode_cfg.noise``), and the generator is left where the reference leaves it: after as many draws as its
         loop makes iterations.  With the same seed the sampled tokens are then the reference's (up to f32 near-ties of
-        ``p / q``).  False: the counter-based hash keyed on ``(seed, window_uid)``, which does not depend on the batch."""
+        ``p / q``).  False: the counter-based hash keyed on ``(seed, window_uid)``, which does not depend on the batch.
+
+        The windows' initial tokens may differ in length (``ragged_decode``), and ``sot_index`` may be one value or one per
+        window: every window then computes what it computes as a job of its own (``swx_decode_cfg.sample_begins``), and
+        ``sample_begin`` comes back as an int array ``[W]`` instead of an int."""
         W = len(init_tokens)
-        n_init = len(init_tokens[0])
-        assert all(len(t) == n_init for t in init_tokens), "all windows of a job share the initial length"
+        begins = [len(t) for t in init_tokens]
+        n_init = max(begins)
+        sots = [int(i) for i in sot_index] if isinstance(sot_index, (list, tuple, np.ndarray)) else [int(sot_index)] * W
+        assert len(sots) == W, "one sot_index per window"
+        uniform = min(begins) == n_init and min(sots) == max(sots)
+        assert uniform or not torch_rng, "torch_rng draws for one window per call"
         self.reserve(max(W, self.max_windows), max(W * n_group, self.max_rows))
         bad = [t for t in suppress_tokens if not 0 <= int(t) < self.dims.n_vocab]
         if bad:       # upstream's SuppressTokens indexes the logits with them: IndexError
@@ -256,15 +268,19 @@ class Engine:
             noise, rng = self._draw_noise(int(sample_len), W * n_group)
         cfg = swx_decode_cfg(
             n_windows=W, n_group=n_group, beam=int(beam), temperature=float(temperature),
-            patience=float(patience or 0.0), sample_len=int(sample_len), sample_begin=n_init, sot_index=int(sot_index),
+            patience=float(patience or 0.0), sample_len=int(sample_len), sample_begin=n_init, sot_index=sots[0],
             suppress_blank=int(suppress_blank), apply_timestamp_rules=int(apply_timestamp_rules),
             max_initial_timestamp_index=-1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index),
             eot=eot, sot=sot, no_timestamps=no_timestamps, timestamp_begin=timestamp_begin, no_speech=no_speech,
             blank_token=blank_token, n_suppress=len(suppress_tokens), min_tokens=int(min_tokens), seed=int(seed),
-            window_uid=uid, noise=_ptr(noise))
+            window_uid=uid, noise=_ptr(noise),
+            sample_begins=None if uniform else _i32arr(begins), sot_indices=None if uniform else _i32arr(sots))
         g_out = self.lib.swx_decode_gout(ctypes.byref(cfg))
         TS = self.dims.n_text_ctx + 1
-        d_init = torch.tensor(np.asarray(init_tokens, dtype=np.int32), device=self.device)
+        h_init = np.full((W, n_init), eot, dtype=np.int32)       # rows shorter than the longest are padded (swx.h)
+        for w, t in enumerate(init_tokens):
+            h_init[w, :len(t)] = t
+        d_init = torch.tensor(h_init, device=self.device)
         d_sup = torch.tensor(np.asarray(list(suppress_tokens) or [0], dtype=np.int32), device=self.device)
         d_mask = None
         if ts_mask is not None:
@@ -277,7 +293,8 @@ class Engine:
         steps = check(self.lib.swx_decode(self.h, ctypes.byref(cfg), _ptr(d_init), _ptr(d_sup), _ptr(d_mask), _ptr(xkv),
                                           _ptr(toks), _ptr(lens), _ptr(sumlp), _ptr(nosp), self.stream), "swx_decode")
         out = dict(tokens=toks.cpu().numpy(), lens=lens.cpu().numpy(), sum_logprobs=sumlp.cpu().numpy(),
-                   no_speech_prob=nosp.cpu().numpy(), steps=steps, sample_begin=n_init)
+                   no_speech_prob=nosp.cpu().numpy(), steps=steps,
+                   sample_begin=n_init if uniform else np.asarray(begins, dtype=np.int64))
         if rng is not None:
             gen, off0, inc = rng
             gen.set_offset(off0 + inc * reference_loop_iterations(out["lens"], n_init, int(sample_len), self.dims.n_text_ctx))

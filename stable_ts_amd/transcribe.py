@@ -24,7 +24,7 @@ import torch
 from .stabilization import host_single_thread
 from .audio import CHUNK_LENGTH, HOP_LENGTH, N_FRAMES, N_SAMPLES, N_SAMPLES_PER_TOKEN, SAMPLE_RATE
 from .audio_io import AudioLoader, audioloader_not_supported, prep_audio
-from .decoding import DecodingOptions, DecodingPlan, DecodingResult
+from .decoding import DecodingOptions, DecodingPlan, DecodingResult, use_ragged
 from .result import WhisperResult
 from .timing import APPEND_PUNCTUATIONS, PREPEND_PUNCTUATIONS, add_word_timestamps_batch
 from .tokenizer import get_tokenizer
@@ -103,12 +103,19 @@ def _decode_with_fallback(model, xkv, base: dict, temperatures: Sequence[float],
         options = DecodingOptions(**kw, temperature=t)
         sub = _xkv_select(model, xkv, pending)
         plans = [DecodingPlan(model, replace(options, prompt=(list(prompts[w]) if prompts[w] else None))) for w in pending]
+        # one lockstep job for all pending windows, whatever the lengths of their prompts, on an engine that runs ragged jobs
+        # (decoding.use_ragged); otherwise one job per distinct initial length
+        ragged = use_ragged(model)
         groups = {}
         for k, p in enumerate(plans):
-            groups.setdefault((p.sample_begin, p.sample_len, p.options.min_tokens), []).append(k)
+            key = (p.sample_len, p.options.min_tokens) if ragged else (p.sample_begin, p.sot_index, p.sample_len, p.options.min_tokens)
+            groups.setdefault(key, []).append(k)
         outs: List[Optional[DecodingResult]] = [None] * len(pending)
-        for _, ks in groups.items():       # one lockstep job per distinct initial length
-            sub_k = _xkv_select(model, sub, ks)
+        for _, ks in groups.items():
+            sub_k = sub if len(ks) == len(pending) else _xkv_select(model, sub, ks)
+            kw_e = plans[ks[0]].engine_kwargs()
+            if len({(plans[k].sample_begin, plans[k].sot_index) for k in ks}) > 1:
+                kw_e["sot_index"] = [plans[k].sot_index for k in ks]
             masks = None
             if ts_masks is not None:
                 masks = torch.stack([ts_masks[pending[k]] for k in ks])
@@ -116,7 +123,7 @@ def _decode_with_fallback(model, xkv, base: dict, temperatures: Sequence[float],
             out = model.engine.decode(sub_k, [list(plans[k].initial_tokens) for k in ks], ts_mask=masks,
                                       window_uid=None if uids is None else [uids[pending[k]] for k in ks],
                                       **(dict(torch_rng=True) if torch_rng and t > 0 and W == 1 else {}),
-                                      **plans[ks[0]].engine_kwargs())
+                                      **kw_e)
             for k, r in zip(ks, plans[ks[0]].results(out, [None] * len(ks), [options.language or "en"] * len(ks))):
                 outs[k] = r
         nxt = []
