@@ -87,6 +87,11 @@ int swx_log_mel(swx_model *m, const float *d_pcm, int B, float *d_mel, int per_i
  * batched call in refine does); frames >= n_total/160 are 0.0.  Returns -2 on a length out of range. */
 int swx_log_mel_ragged(swx_model *m, const float *d_pcm, const int32_t *n_valid, const int32_t *n_total, int B,
                        float *d_mel, int per_item_max, void *stream);
+/* the same with the clamp floor shared by every `group` CONSECUTIVE items (B % group == 0, else "invalid argument"): refine in
+ * lockstep puts the two audio copies of several word groups into one batch, and upstream's batched call takes the floor from
+ * the pair (alignment.py:660).  group == 1 is per_item_max != 0, group == B is per_item_max == 0, bit for bit. */
+int swx_log_mel_ragged_grouped(swx_model *m, const float *d_pcm, const int32_t *n_valid, const int32_t *n_total, int B,
+                               float *d_mel, int group, void *stream);
 
 /* ---- a2: encoder (replaces model.encoder(mel), decode.py:27-30, timing.py:59-60)
  * d_mel f32 [B][n_mels][3000] -> d_xa [B][1500][d] in the compute dtype */
@@ -216,6 +221,19 @@ int swx_weighted_sum(const float *const *h_xs, const float *h_coef, int n_in, fl
  * with tokens = [[sot]]. */
 int swx_forward_logits(swx_model *m, const int32_t *d_tokens, const int32_t *h_n_tok, int W, int max_n,
                        const void *d_xkv, float *d_logits, void *stream);
+
+/* the same pass reduced to what refine's bisection reads (non_whisper/refinement.py:289-327): for every window w and row
+ * j < n_tok[w] - 1, with x = the logits row swx_forward_logits defines and t = d_tokens[w][j + 1],
+ *  d_prob f32   [W][max_n]  softmax(x[:n_vocab_used])[t] -- the arithmetic of swx_score's d_token_probs
+ *  d_rank int32 [W][max_n]  #{v < n_vocab_used : x_v < x_t or (x_v == x_t and v < t)}: the position of t in an ascending sort
+ *                           of the row on (logit, index), a total order.  The reference sorts the f32 PROBABILITIES with an
+ *                           unstable sort; the two differ only where rounding to f32 probabilities ties another entry with the
+ *                           target itself, and there the reference's position is arbitrary.
+ * A target outside [0, n_vocab_used) gives prob 0, rank -1; entries j >= n_tok[w] - 1 are not written.  Output is O(W * max_n):
+ * the projection runs in row chunks through the bound workspace and a reduction kernel finishes each chunk.  A window's
+ * values do not depend on the batch it runs in. */
+int swx_forward_token_ranks(swx_model *m, const int32_t *d_tokens, const int32_t *h_n_tok, int W, int max_n, int n_vocab_used,
+                            const void *d_xkv, float *d_prob, int32_t *d_rank, void *stream);
 
 /* ---- a7 stand-alone (test hook + extra_models path): weights f32 [W][H][N][ld_f] raw qk ->
  * neg_matrix f32 [W][N][1500].  d_scratch: swx_align_weights_scratch_bytes(W, H, N) bytes of device memory (no entry point of

@@ -57,6 +57,7 @@ SYMBOLS = {
     "swx_bind_workspace": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int]),
     "swx_log_mel": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "swx_log_mel_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "swx_log_mel_ragged_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "swx_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "swx_cross_kv_bytes": (c_size_t, [c_void_p, c_int]),
     "swx_cross_kv": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
@@ -76,6 +77,8 @@ SYMBOLS = {
                               c_float, c_float, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "swx_weighted_sum": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
     "swx_forward_logits": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "swx_forward_token_ranks": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
     "swx_align_weights_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "swx_align_weights": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int32), c_float, c_int, c_void_p,
                                   c_void_p, c_size_t, c_void_p]),

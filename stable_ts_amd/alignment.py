@@ -8,7 +8,7 @@ restatement of the reference's window state machine (non_whisper/alignment.py:58
 ``token_step``, gap padding, non-speech skipping, the re-alignment policy of ``_fallback``), which is tested against
 the reference's own class on CPU (tests/test_aligner_cpu.py).
 """
-from typing import List, Optional, Sequence, Union
+from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -61,6 +61,8 @@ def make_refinement_func(model, tokenizer):
     """alignment.py:636-672 (seam B3): ``inference_func(audio_segment f32[2, n], tokens) -> probabilities
     [2, len(tokens), eot]`` over the text vocabulary, a device tensor.  Both audio copies go through mel -> encoder ->
     cross-KV and ONE teacher-forced decoder pass of ``sot_sequence + [no_timestamps] + tokens + [eot]``.
+    ``inference_func.batch`` is the native form ``refine(batch_size=N)`` drives: the probes of several word groups in one pass,
+    answered with ``(probability, rank)`` per token instead of a distribution.
     Like the reference the log-mel is computed on the un-padded segment and the remaining frames are filled with 0.0
     (``pad_or_trim`` of the mel, not of the audio).  Host-side bisection: stable_ts_amd/refiner.py (CPU-tested against
     the reference's Refiner); the callable is CPU-tested against the reference's on the engine stand-in
@@ -75,6 +77,26 @@ def make_refinement_func(model, tokenizer):
         logits = model.engine.forward_logits(xkv, [ids, ids])
         return logits[:, len(sot): len(sot) + len(tokens), : tokenizer.eot].softmax(dim=-1)
 
+    def inference_batch(items: Sequence[Tuple[torch.Tensor, List[int]]]) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+        """[(audio[2, n_g], tokens_g)] -> [(p[2, T_g], rank[2, T_g])] (host tensors): ONE mel / encoder / cross-KV / decoder
+        pass over all 2 G windows, ragged in audio length and token count.  Each pair of copies keeps its own log-mel clamp
+        floor (``swx_log_mel_ragged_grouped``), and of every row of the pass only the target token's probability and its rank
+        in the row leave the device (``swx_forward_token_ranks``) -- the two numbers per token the bisection reads."""
+        if not items:
+            return []
+        segs, ids = [], []
+        for audio_segment, tokens in items:
+            audio_segment = audio_segment[..., :N_SAMPLES]
+            segs += [audio_segment[0], audio_segment[1]]
+            ids += [[*sot, tokenizer.no_timestamps, *[int(t) for t in tokens], tokenizer.eot]] * 2
+        mel = model.log_mel_segments(segs, group=2)
+        xkv = model.cross_kv(model.encoder(mel))
+        prob, rank = model.engine.forward_token_ranks(xkv, ids, n_vocab_used=tokenizer.eot)
+        prob, rank = prob.cpu(), rank.cpu()
+        return [(prob[2 * g: 2 * g + 2, len(sot): len(sot) + len(tokens)], rank[2 * g: 2 * g + 2, len(sot): len(sot) + len(tokens)])
+                for g, (_, tokens) in enumerate(items)]
+
+    inference_func.batch = inference_batch
     return inference_func
 
 
@@ -159,10 +181,17 @@ def align_words(model, audio, result: Union[WhisperResult, List[dict]], language
 def refine(model, audio, result: WhisperResult, *, steps: str = None, rel_prob_decrease: float = .03,
            abs_prob_decrease: float = .05, rel_rel_prob_decrease: Optional[float] = None, prob_threshold: float = .5,
            rel_dur_change: Optional[float] = .5, abs_dur_change: Optional[float] = None, word_level: bool = True,
-           precision: float = None, single_batch: bool = False, inplace: bool = True, **options) -> WhisperResult:
+           precision: float = None, single_batch: bool = False, inplace: bool = True, batch_size: Optional[int] = None,
+           **options) -> WhisperResult:
     """alignment.py:512-635: move word starts later / ends earlier as far as the token probabilities allow.  The
     bisection is :class:`stable_ts_amd.refiner.Refiner`; ``single_batch`` is accepted for signature compatibility (the
-    two audio copies always share one batched pass here)."""
+    two audio copies always share one batched pass here).
+
+    ``batch_size``: None = one word group after the other, each probe a full-vocabulary distribution handed to the host
+    logic (the reference's order of calls).  N >= 1 = the native probe (``swx_forward_token_ranks``: a probability and a rank
+    per token leave the device) with up to N word groups of a step bisected in lockstep, 2 N windows per device pass; 1 is
+    the native probe group by group.  The workspace grows to the 2 * min(N, groups) windows a round really holds
+    (DESIGN.md section 8 lists the memory per N)."""
     from .refiner import Refiner
     from .transcribe import as_waveform, pop_audio_options
     audio_options = pop_audio_options(options)
@@ -179,5 +208,5 @@ def refine(model, audio, result: WhisperResult, *, steps: str = None, rel_prob_d
                       rel_prob_decrease=rel_prob_decrease, abs_prob_decrease=abs_prob_decrease,
                       rel_rel_prob_decrease=rel_rel_prob_decrease, prob_threshold=prob_threshold,
                       rel_dur_change=rel_dur_change, abs_dur_change=abs_dur_change, word_level=word_level,
-                      precision=precision, max_inference_tokens=model.dims.n_text_ctx - 6, **options)
+                      precision=precision, max_inference_tokens=model.dims.n_text_ctx - 6, batch_size=batch_size, **options)
     return refiner.refine(as_waveform(audio, **audio_options), result, inplace)

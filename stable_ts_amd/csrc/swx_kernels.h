@@ -225,7 +225,7 @@ int swx_align_weights_launch(const float *d_qk, float *d_p, float *d_mean, float
 int swx_mel_launch(const float *d_pcm, int B, const float *d_hann, const double2 *d_twiddle, const float *d_filters,
                    int n_mels, float *d_mel, unsigned *d_gmax, int per_item_max, hipStream_t s);
 int swx_mel_ragged_launch(const float *d_pcm, const int *d_lens, int B, const float *d_hann, const double2 *d_twiddle,
-                          const float *d_filters, int n_mels, float *d_mel, unsigned *d_gmax, int per_item_max,
+                          const float *d_filters, int n_mels, float *d_mel, unsigned *d_gmax, int group,
                           hipStream_t s);
 
 // ---- swx_headsel.hip: the head-selection variants of the word-timestamp stage from the captured cross-attention queries

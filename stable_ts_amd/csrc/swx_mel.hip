@@ -115,16 +115,14 @@ __global__ __launch_bounds__(256) void swx_mel_power_kernel(const float *__restr
 
 template <bool RAGGED>
 __global__ __launch_bounds__(256) void swx_mel_finish_kernel(float *__restrict__ out, const unsigned *__restrict__ gmax,
-                                                             int B, int per_window, size_t per_item,
+                                                             int group, size_t per_item,
                                                              const int2 *__restrict__ lens)
 {
-    const int b = blockIdx.y;
-    float mx;
-    if (per_window) mx = ordered_to_f32(gmax[b]);
-    else {
-        mx = -__builtin_inff();
-        for (int i = 0; i < B; ++i) mx = fmaxf(mx, ordered_to_f32(gmax[i]));
-    }
+    // the clamp floor is shared by the `group` consecutive items b belongs to (1: per window, B: the whole batch; a max, so the
+    // order of the walk is free)
+    const int b = blockIdx.y, g0 = b - b % group;
+    float mx = -__builtin_inff();
+    for (int i = g0; i < g0 + group; ++i) mx = fmaxf(mx, ordered_to_f32(gmax[i]));
     const float floor_v = mx - 8.0f;
     float *o = out + (size_t)b * per_item;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < per_item; i += (size_t)gridDim.x * 256) {
@@ -145,7 +143,7 @@ int swx_mel_launch(const float *d_pcm, int B, const float *d_hann, const double2
     if (e != hipSuccess) return -100 - (int)e;
     hipLaunchKernelGGL(swx_mel_power_kernel<false>, dim3(MEL_NFRAMES / MEL_FB, B), dim3(256), 0, s, d_pcm, d_hann,
                        d_twiddle, d_filters, n_mels, d_mel, d_gmax, (const int2 *)nullptr);
-    hipLaunchKernelGGL(swx_mel_finish_kernel<false>, dim3(64, B), dim3(256), 0, s, d_mel, d_gmax, B, per_item_max,
+    hipLaunchKernelGGL(swx_mel_finish_kernel<false>, dim3(64, B), dim3(256), 0, s, d_mel, d_gmax, per_item_max ? 1 : B,
                        (size_t)n_mels * MEL_NFRAMES, (const int2 *)nullptr);
     SWX_CHECK_LAUNCH();
     return 0;
@@ -154,16 +152,17 @@ int swx_mel_launch(const float *d_pcm, int B, const float *d_hann, const double2
 // d_lens: int32 [B][2] = {n_valid, n_total}; 200 < n_total, n_valid <= min(n_total, 480000), n_total/160 <= 3008
 // (checked by the caller, swx_log_mel_ragged).  One extra block row covers the frames 3000..3007 that only feed the max.
 int swx_mel_ragged_launch(const float *d_pcm, const int *d_lens, int B, const float *d_hann, const double2 *d_twiddle,
-                          const float *d_filters, int n_mels, float *d_mel, unsigned *d_gmax, int per_item_max,
+                          const float *d_filters, int n_mels, float *d_mel, unsigned *d_gmax, int group,
                           hipStream_t s)
 {
     if (B <= 0) return 0;
+    if (group <= 0 || B % group) return -1;     // `group` consecutive items share one clamp floor
     SwxProfScope prof(PC_MEL, (double)B * (480000.0 * 4 + (double)n_mels * 3000 * 4), s);
     hipError_t e = hipMemsetAsync(d_gmax, 0, sizeof(unsigned) * B, s);
     if (e != hipSuccess) return -100 - (int)e;
     hipLaunchKernelGGL(swx_mel_power_kernel<true>, dim3(MEL_NFRAMES / MEL_FB + 1, B), dim3(256), 0, s, d_pcm, d_hann,
                        d_twiddle, d_filters, n_mels, d_mel, d_gmax, (const int2 *)d_lens);
-    hipLaunchKernelGGL(swx_mel_finish_kernel<true>, dim3(64, B), dim3(256), 0, s, d_mel, d_gmax, B, per_item_max,
+    hipLaunchKernelGGL(swx_mel_finish_kernel<true>, dim3(64, B), dim3(256), 0, s, d_mel, d_gmax, group,
                        (size_t)n_mels * MEL_NFRAMES, (const int2 *)d_lens);
     SWX_CHECK_LAUNCH();
     return 0;

@@ -656,29 +656,57 @@ swx_model::StepGraph *step_graph(swx_model *m, const DecodeBufs &b, const void *
     return &m->graphs.back();
 }
 
-__global__ __launch_bounds__(256) void token_prob_kernel(const float *__restrict__ logits, int V, int eot,
-                                                         const int32_t *__restrict__ target_tok, float *__restrict__ out)
+// one block per row: out[row] = softmax(logits[row][:n_used])[target].  RANK (swx_forward_token_ranks): also rank[row] =
+// #{v < n_used : x_v < x_t or (x_v == x_t and v < t)}, the position of the target in an ascending sort on (logit, index),
+// counted next to the maximum pass (integer sums: their order is free).  The probability is ONE code path for both
+// instantiations -- the same per-thread elements, butterfly and LDS combine -- so swx_score's token probabilities and
+// swx_forward_token_ranks' agree bit for bit on the same logits.  A target outside [0, n_used): probability 0, rank -1.
+template <bool RANK>
+__global__ __launch_bounds__(256) void token_prob_kernel(const float *__restrict__ logits, int V, int n_used,
+                                                         const int32_t *__restrict__ target_tok, float *__restrict__ out,
+                                                         int32_t *__restrict__ rank)
 {
-    // one block per row: softmax(logits[row][:eot])[target]
     __shared__ float sh[4];
+    __shared__ int shc[4];
     const int row = blockIdx.x, tid = threadIdx.x;
     const float *lg = logits + (size_t)row * V;
+    int t = 0, below = 0;
+    bool ok = false;
+    float xt = 0.f;
+    if constexpr (RANK) {
+        t = target_tok[row];
+        ok = t >= 0 && t < n_used;
+        xt = ok ? lg[t] : 0.f;
+    }
     float mx = -__builtin_inff();
-    for (int i = tid; i < eot; i += 256) mx = fmaxf(mx, lg[i]);
+    for (int i = tid; i < n_used; i += 256) {
+        const float v = lg[i];
+        mx = fmaxf(mx, v);
+        if constexpr (RANK) below += (v < xt || (v == xt && i < t)) ? 1 : 0;
+    }
     mx = wave_max(mx);
+    if constexpr (RANK) {
+        const int lane = tid & 63;
+        below += lane_xor<32>(below, lane); below += lane_xor<16>(below, lane); below += lane_xor<8>(below, lane);
+        below += lane_xor<4>(below, lane); below += lane_xor<2>(below, lane); below += lane_xor<1>(below, lane);
+        if (lane == 0) shc[tid >> 6] = below;
+    }
     if ((tid & 63) == 0) sh[tid >> 6] = mx;
     __syncthreads();
     mx = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+    if constexpr (RANK) below = shc[0] + shc[1] + shc[2] + shc[3];
     __syncthreads();
     float sum = 0.f;
-    for (int i = tid; i < eot; i += 256) sum += expf(lg[i] - mx);
+    for (int i = tid; i < n_used; i += 256) sum += expf(lg[i] - mx);
     sum = wave_sum(sum);
     if ((tid & 63) == 0) sh[tid >> 6] = sum;
     __syncthreads();
     sum = sh[0] + sh[1] + sh[2] + sh[3];
     if (tid == 0) {
-        const int t = target_tok[row];
-        out[row] = (t >= 0 && t < eot) ? expf(lg[t] - mx) / sum : 0.f;
+        if constexpr (!RANK) t = target_tok[row];
+        const bool in = t >= 0 && t < n_used;
+        out[row] = in ? expf(lg[t] - mx) / sum : 0.f;
+        if constexpr (RANK) rank[row] = in ? below : -1;
     }
 }
 
@@ -1003,12 +1031,13 @@ int swx_log_mel(swx_model *m, const float *d_pcm, int B, float *d_mel, int per_i
                           m->dims.n_mels, d_mel, m->Wp<unsigned>(m->L.gmax), per_item_max, S(stream));
 }
 
-int swx_log_mel_ragged(swx_model *m, const float *d_pcm, const int32_t *n_valid, const int32_t *n_total, int B,
-                       float *d_mel, int per_item_max, void *stream)
+int swx_log_mel_ragged_grouped(swx_model *m, const float *d_pcm, const int32_t *n_valid, const int32_t *n_total, int B,
+                               float *d_mel, int group, void *stream)
 {
     if (!m || !m->arena || !m->ws) return -9;
     if (B <= 0) return 0;
     if (B > m->max_windows) return -8;
+    if (group <= 0 || B % group) return -1;
     if (!n_valid || !n_total) return -2;
     std::vector<int32_t> lens((size_t)B * 2);
     for (int b = 0; b < B; ++b) {
@@ -1025,8 +1054,13 @@ int swx_log_mel_ragged(swx_model *m, const float *d_pcm, const int32_t *n_valid,
     if (e == hipSuccess) e = hipStreamSynchronize(s);   // lens is a stack-lifetime staging buffer
     if (e != hipSuccess) return -100 - (int)e;
     return swx_mel_ragged_launch(d_pcm, d_lens, B, m->A<float>(m->o_hann), m->A<double2>(m->o_twiddle),
-                                 m->A<float>(m->o_filters), m->dims.n_mels, d_mel, m->Wp<unsigned>(m->L.gmax), per_item_max,
-                                 s);
+                                 m->A<float>(m->o_filters), m->dims.n_mels, d_mel, m->Wp<unsigned>(m->L.gmax), group, s);
+}
+
+int swx_log_mel_ragged(swx_model *m, const float *d_pcm, const int32_t *n_valid, const int32_t *n_total, int B,
+                       float *d_mel, int per_item_max, void *stream)
+{
+    return swx_log_mel_ragged_grouped(m, d_pcm, n_valid, n_total, B, d_mel, per_item_max ? 1 : B, stream);
 }
 
 // ----------------------------------------------------------------------------------------------------- encoder
@@ -1467,8 +1501,8 @@ static int score_token_probs(swx_model *m, const int32_t *d_tokens, int W, int m
                 const int nr = (rpw - r0) < chunk ? (rpw - r0) : chunk;
                 const unsigned char *hid = hh + ((size_t)w * max_n + n_sot + r0) * d * e;
                 SWX_TRY(logits_gemm(m, hid, d, nr, lg, s));
-                hipLaunchKernelGGL(token_prob_kernel, dim3(nr), dim3(256), 0, s, lg, D.n_vocab, eot, targets + (size_t)w * rpw + r0,
-                                   d_token_probs + (size_t)w * max_n + r0);
+                hipLaunchKernelGGL(token_prob_kernel<false>, dim3(nr), dim3(256), 0, s, lg, D.n_vocab, eot, targets + (size_t)w * rpw + r0,
+                                   d_token_probs + (size_t)w * max_n + r0, (int32_t *)nullptr);
             }
         }
         SWX_CHECK_LAUNCH();
@@ -1544,6 +1578,42 @@ int swx_forward_logits(swx_model *m, const int32_t *d_tokens, const int32_t *h_n
     const int rows = W * max_n;
     SWX_TRY(swx_layernorm(m->dtype, x, d, m->A<float>(m->o_ln_g), m->A<float>(m->o_ln_b), hh, d, rows, d, s));
     return logits_gemm(m, hh, d, rows, d_logits, s);
+}
+
+// The teacher-forced pass of swx_forward_logits reduced on the device to the two numbers per row refine's bisection reads.  The
+// vocabulary projection runs window by window in 64-row chunks through the workspace's logits region and token_prob_kernel<true> finishes each
+// chunk, so no [W][max_n][n_vocab] tensor exists anywhere.  Row j of window w predicts d_tokens[w][j + 1]: the target list of a
+// chunk is the token row itself, shifted by one.  Only rows j < n_tok[w] - 1 are computed and written.
+int swx_forward_token_ranks(swx_model *m, const int32_t *d_tokens, const int32_t *h_n_tok, int W, int max_n, int n_vocab_used,
+                            const void *d_xkv, float *d_prob, int32_t *d_rank, void *stream)
+{
+    if (!m || !m->arena || !m->ws) return -9;
+    if (W <= 0) return 0;
+    if (!d_tokens || !h_n_tok || !d_prob || !d_rank) return -1;
+    const swx_dims &D = m->dims;
+    if (n_vocab_used <= 0 || n_vocab_used > D.n_vocab) return -1;
+    hipStream_t s = S(stream);
+    const int d = D.n_text_state;
+    const size_t e = m->esz;
+    SWX_TRY(score_forward(m, d_tokens, h_n_tok, W, max_n, 0, 0, max_n, d_xkv, false, s));
+    unsigned char *x = m->ws + m->L.x, *hh = m->ws + m->L.h;
+    SWX_TRY(swx_layernorm(m->dtype, x, d, m->A<float>(m->o_ln_g), m->A<float>(m->o_ln_b), hh, d, W * max_n, d, s));
+    float *lg = m->Wp<float>(m->L.logits);
+    // a fixed chunk (the logits region always holds 64 rows): the projection's launch shapes then depend on the window's own
+    // token count alone, never on the workspace that happens to be bound or on the batch around the window
+    const int chunk = 64;
+    for (int w = 0; w < W; ++w) {
+        const int rows = h_n_tok[w] - 1;
+        for (int r0 = 0; r0 < rows; r0 += chunk) {
+            const int nr = (rows - r0) < chunk ? (rows - r0) : chunk;
+            const size_t at = (size_t)w * max_n + r0;
+            SWX_TRY(logits_gemm(m, hh + at * d * e, d, nr, lg, s));
+            hipLaunchKernelGGL(token_prob_kernel<true>, dim3(nr), dim3(256), 0, s, lg, D.n_vocab, n_vocab_used, d_tokens + at + 1,
+                               d_prob + at, d_rank + at);
+            SWX_CHECK_LAUNCH();
+        }
+    }
+    return 0;
 }
 
 // ------------------------------------------------------------------------------- head-selection variants (f4)

@@ -193,14 +193,19 @@ class Engine:
         return mel
 
     def log_mel_ragged(self, pcm: torch.Tensor, n_valid: Sequence[int], n_total: Sequence[int],
-                       per_item_max: bool = True) -> torch.Tensor:
+                       per_item_max: bool = True, group: Optional[int] = None) -> torch.Tensor:
         """pcm f32 [B, 480000] (row b holds n_valid[b] samples) -> pad_or_trim(log_mel(segment, padding=n_total-n_valid),
-        3000): upstream's frames for a segment that is not padded to 30 s (refine / locate)."""
+        3000): upstream's frames for a segment that is not padded to 30 s (refine / locate).  ``group``: every ``group``
+        consecutive items share one clamp floor (``swx_log_mel_ragged_grouped``); None = ``per_item_max`` decides."""
         assert pcm.is_cuda and pcm.dtype == torch.float32 and pcm.shape[-1] == N_SAMPLES and pcm.is_contiguous()
         B = pcm.shape[0]
         assert len(n_valid) == B and len(n_total) == B
         self.reserve(max(B, self.max_windows), max(self.max_rows, 1))
         mel = torch.empty(B, self.dims.n_mels, N_FRAMES, dtype=torch.float32, device=self.device)
+        if group is not None:
+            check(self.lib.swx_log_mel_ragged_grouped(self.h, _ptr(pcm), _i32arr(n_valid), _i32arr(n_total), B, _ptr(mel),
+                                                      int(group), self.stream), "swx_log_mel_ragged_grouped")
+            return mel
         check(self.lib.swx_log_mel_ragged(self.h, _ptr(pcm), _i32arr(n_valid), _i32arr(n_total), B, _ptr(mel),
                                           int(per_item_max), self.stream),
               "swx_log_mel_ragged")
@@ -457,6 +462,27 @@ class Engine:
         check(self.lib.swx_forward_logits(self.h, _ptr(d_tok), _i32arr(n_tok), W, max_n, _ptr(xkv), _ptr(out),
                                           self.stream), "swx_forward_logits")
         return out
+
+    def forward_token_ranks(self, xkv: torch.Tensor, tokens: Sequence[Sequence[int]], n_vocab_used: Optional[int] = None,
+                            pad_token: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The teacher-forced pass of ``forward_logits`` reduced on the device (``swx_forward_token_ranks``): per window w and
+        row j < len(tokens[w]) - 1 the probability of ``tokens[w][j + 1]`` under ``softmax(logits[w, j, :n_vocab_used])`` and
+        its position in an ascending sort of that row on (logit, index).  Returns (prob f32 [W, max_n], rank int32 [W, max_n])
+        on the device; entries past a window's last predicting row are 0 / -1."""
+        W = len(tokens)
+        n_tok = [len(t) for t in tokens]
+        max_n = max(n_tok)
+        self.reserve(max(W, self.max_windows), max(self.max_rows, 1))
+        pad = np.full((W, max_n), pad_token, dtype=np.int32)
+        for w, t in enumerate(tokens):
+            pad[w, :len(t)] = t
+        d_tok = torch.tensor(pad, device=self.device)
+        prob = torch.zeros(W, max_n, dtype=torch.float32, device=self.device)
+        rank = torch.full((W, max_n), -1, dtype=torch.int32, device=self.device)
+        used = self.dims.n_vocab if n_vocab_used is None else int(n_vocab_used)
+        check(self.lib.swx_forward_token_ranks(self.h, _ptr(d_tok), _i32arr(n_tok), W, max_n, used, _ptr(xkv), _ptr(prob),
+                                               _ptr(rank), self.stream), "swx_forward_token_ranks")
+        return prob, rank
 
     # ------------------------------------------------------------------ a8 dtw
     def dtw(self, x: torch.Tensor, N: Sequence[int], M: Sequence[int]):

@@ -16,6 +16,14 @@ The bisection state lives in int32 sample arrays exactly like the reference's (`
 its quirks, which are part of the observable behaviour: the "original" probability a word is compared with is
 overwritten by the latest probe (``new_probs`` aliases ``orig_probs``, :405, 472), and the audio copy a word mutes is
 looked up in the per-TOKEN row table with the WORD index (:424).
+
+One group's bisection is a generator (``_group_rounds``) that yields "probe this" and receives the picked ``(p, rank)``.
+Within one step the groups are independent (every bound is computed up front, a group reads and writes only its own
+words), so two drivers run the SAME generator: the sequential one (``batch_size=None``, the reference's order of calls)
+and the lockstep one (``batch_size=N``), which keeps up to N unfinished groups in flight and hands all their probes of a
+round to ``inference_func.batch`` in one call (``stable_ts_amd.alignment.make_refinement_func``: one mel / encoder /
+decoder pass over 2 N windows, answered by ``swx_forward_token_ranks`` with a probability and a rank per token instead of a
+distribution).  A group leaves the batch when all its words are done and a waiting group takes its place.
 """
 import copy
 from typing import Callable, Iterator, List, Optional, Tuple
@@ -26,14 +34,27 @@ import torch
 from .result import WhisperResult, WordTiming
 
 
+def token_rank(row, target: int) -> int:
+    """The rank the native probe reports (``swx_forward_token_ranks``): the position of ``target`` in an ascending sort of
+    ``row`` on (value, index) -- ``#{v : row[v] < row[target] or (row[v] == row[target] and v < target)}``.  A total order, so
+    it is what a STABLE ascending sort gives; an unstable sort (the reference's ``dist.sort()``) may differ from it only where
+    another entry ties with the target itself."""
+    row = np.asarray(row)
+    x = row[target]
+    return int(np.count_nonzero(row < x) + np.count_nonzero(row[:target] == x))
+
+
 class Refiner:
     def __init__(self, inference_func: Callable, sample_rate: int = 16000, max_segment_length="30s",
                  max_inference_tokens: int = 100, *, steps: str = "se", rel_prob_decrease: float = .03,
                  abs_prob_decrease: float = .05, rel_rel_prob_decrease: Optional[float] = None,
                  prob_threshold: float = .5, rel_dur_change: Optional[float] = .5,
                  abs_dur_change: Optional[float] = None, word_level: bool = True, precision: Optional[float] = None,
-                 progress_callback: Optional[Callable] = None, **unsupported):
+                 progress_callback: Optional[Callable] = None, batch_size: Optional[int] = None, **unsupported):
         steps = steps or "se"
+        if batch_size is not None and (isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1):
+            raise ValueError(f"batch_size must be None or an integer >= 1, got {batch_size!r}")
+        self.batch_size = None if batch_size is None else int(batch_size)
         bad = steps.replace("s", "").replace("e", "")
         if bad:
             raise ValueError(f'Invalid step(s): {", ".join(bad)}')
@@ -126,7 +147,18 @@ class Refiner:
                at_end: bool):
         """One inference call -> per word the probability of its first (last, for end refinement) token in the audio
         copy that word owns, and that token's rank among the vocabulary when the function returns a distribution."""
-        p: torch.Tensor = self.inference_func(audio2, text_tokens)
+        return self._pick(self.inference_func(audio2, text_tokens), text_tokens, word_tokens, rows, at_end)
+
+    def _pick(self, p, text_tokens: List[int], word_tokens: List[List[int]], rows: List[int], at_end: bool):
+        """What one probe's output says about every word.  Three forms: probabilities ``[2, T]`` (no ranks), distributions
+        ``[2, T, vocab]`` (ranks from a sort, as the reference), or a pair ``(p [2, T], rank [2, T])`` whose ranks were
+        computed where the distribution lived (position of the token in an ascending order of its row)."""
+        rank_t = None
+        if isinstance(p, (tuple, list)):
+            p, rank_t = p
+            if p.ndim != 2 or tuple(rank_t.shape) != tuple(p.shape):
+                raise RuntimeError(f"expected probabilities and ranks of one 2-D shape but got {tuple(p.shape)} and "
+                                   f"{tuple(rank_t.shape)}")
         if p.size(0) != 2:
             raise RuntimeError(f"expected dim 0 to be length of 2 but got {p.size(0)}")
         if p.size(1) != len(text_tokens):
@@ -136,7 +168,11 @@ class Refiner:
         pos = torch.arange(len(text_tokens))
         bounds = np.pad(np.cumsum([len(t) for t in word_tokens]), (1, 0))
         pick = [(j - 1 if at_end else i) for i, j in zip(bounds[:-1], bounds[1:])]
-        if p.ndim == 2:
+        if rank_t is not None:
+            tok_p = p[rows, pos].tolist()
+            where = rank_t[rows, pos].tolist()
+            ranks = [int(where[k]) for k in pick]
+        elif p.ndim == 2:
             tok_p = p[rows, pos].tolist()
             ranks = [0] * len(word_tokens)
         else:
@@ -168,92 +204,141 @@ class Refiner:
     def _refine(self, result: WhisperResult, step: str):
         total_duration = round(self._audio.shape[-1] / self.sample_rate, 3)
         at_end = step == "e"
-        for words, g_lo, g_hi, edge in self._groups(result, total_duration):
-            offset = g_lo[0]
-            a, b = round(offset * self.sample_rate), round(g_hi[-1] * self.sample_rate)
-            clean = self._audio[a:b + 1].unsqueeze(0)
-            max_start = self._samples([w.end for w in words], offset)
-            min_end = self._samples([w.start for w in words], offset)
-            min_start = self._samples(g_lo, offset)
-            max_end = self._samples(g_hi, offset)
-            mid_start = min_start + ((max_start - min_start) / 2).round().astype(np.int32)
-            mid_end = min_end + ((max_end - min_end) / 2).round().astype(np.int32)
-            text_tokens = [t for w in words for t in w.tokens]
-            word_tokens = [list(w.tokens) for w in words]
-            probe = clean.clone().repeat_interleave(2, 0)               # copy 0: even words, copy 1: odd words
-            done = np.less([w.probability for w in words], self.prob_threshold)
-            done = np.logical_or(done, [w.duration == 0 for w in words])
-            if not self.word_level:
-                done[edge != (2 if at_end else 1)] = True
-            rows: List[int] = []
-            for idx, cut in enumerate(max_start if at_end else min_end):
-                row = idx % 2
-                rows.extend([row] * len(words[idx].tokens))
+        if self.batch_size is not None:
+            return self._refine_lockstep(result, total_duration, at_end)
+        for group in self._groups(result, total_duration):
+            rounds = self._group_rounds(*group, at_end)
+            request = next(rounds)
+            while True:
+                try:
+                    request = rounds.send(self._probe(*request, at_end))
+                except StopIteration:
+                    break
+
+    def _infer_batch(self, requests: list) -> list:
+        """The probes of one lockstep round, one per group in flight: through ``inference_func.batch`` where the function
+        has one (one device pass for all of them), else call by call."""
+        batch = getattr(self.inference_func, "batch", None)
+        if batch is None:
+            return [self.inference_func(r[0], r[1]) for r in requests]
+        outs = batch([(r[0], r[1]) for r in requests])
+        if len(outs) != len(requests):
+            raise RuntimeError(f"expected {len(requests)} outputs from inference_func.batch but got {len(outs)}")
+        return outs
+
+    def _refine_lockstep(self, result: WhisperResult, total_duration: float, at_end: bool):
+        """Up to ``batch_size`` unfinished groups advance one bisection round per inference call.  Every group runs the
+        generator the sequential driver runs and sees its own probes in its own order, so the timestamps are the
+        sequential ones whenever a probe's answer does not depend on the batch it was computed in."""
+        waiting = iter(list(self._groups(result, total_duration)))
+        flying: list = []                                                # [generator, its pending request]
+        while True:
+            while len(flying) < self.batch_size:
+                group = next(waiting, None)
+                if group is None:
+                    break
+                rounds = self._group_rounds(*group, at_end)
+                flying.append([rounds, next(rounds)])
+            if not flying:
+                return
+            outs = self._infer_batch([request for _, request in flying])
+            still = []
+            for (rounds, request), out in zip(flying, outs):
+                try:
+                    still.append([rounds, rounds.send(self._pick(out, *request[1:], at_end))])
+                except StopIteration:
+                    pass
+            flying = still
+
+    def _group_rounds(self, words: List[WordTiming], g_lo: list, g_hi: list, edge: np.ndarray, at_end: bool):
+        """One group's bisection (:359-475) as a generator: yields ``(audio[2, n], text_tokens, word_tokens, rows)`` -- the
+        arguments of ``_probe`` -- and receives what ``_probe`` returns for it.  The yielded audio is the group's live probe
+        buffer: the driver must be done with it before it sends the answer."""
+        offset = g_lo[0]
+        a, b = round(offset * self.sample_rate), round(g_hi[-1] * self.sample_rate)
+        clean = self._audio[a:b + 1].unsqueeze(0)
+        max_start = self._samples([w.end for w in words], offset)
+        min_end = self._samples([w.start for w in words], offset)
+        min_start = self._samples(g_lo, offset)
+        max_end = self._samples(g_hi, offset)
+        mid_start = min_start + ((max_start - min_start) / 2).round().astype(np.int32)
+        mid_end = min_end + ((max_end - min_end) / 2).round().astype(np.int32)
+        text_tokens = [t for w in words for t in w.tokens]
+        word_tokens = [list(w.tokens) for w in words]
+        probe = clean.clone().repeat_interleave(2, 0)               # copy 0: even words, copy 1: odd words
+        done = np.less([w.probability for w in words], self.prob_threshold)
+        done = np.logical_or(done, [w.duration == 0 for w in words])
+        if not self.word_level:
+            done[edge != (2 if at_end else 1)] = True
+        rows: List[int] = []
+        for idx, cut in enumerate(max_start if at_end else min_end):
+            row = idx % 2
+            rows.extend([row] * len(words[idx].tokens))
+            if done[idx]:
+                continue
+            if at_end:                                               # mute from the word's end to the next word
+                stop = probe.size(-1) if idx == len(words) - 1 else mid_end[idx + 1]
+                probe[row, cut:stop] = 0
+            else:                                                    # mute from the previous word up to the start
+                stop = 0 if idx == 0 else mid_start[idx - 1]
+                probe[row, stop:cut] = 0
+        ref_p, ref_rank = yield probe, text_tokens, word_tokens, rows
+        track = np.zeros((ref_p.shape[-1], 3), dtype=np.int32)       # [failed once, passed once, last good boundary]
+        track[:, -1] = -1
+        first_cut = (mid_end, max_start) if at_end else (min_end, mid_start)
+        for idx, (s, e) in enumerate(zip(*first_cut)):
+            if not done[idx]:
+                probe[idx % 2, s:e] = 0
+        prev_p = ref_p
+        while not np.all(done):
+            p, rank = yield probe, text_tokens, word_tokens, rows
+            abs_drop = ref_p - p
+            rel_drop = abs_drop / ref_p
+            step_drop = (prev_p - p) / prev_p
+            prev_p = p
+            for idx in range(len(words)):
                 if done[idx]:
                     continue
-                if at_end:                                               # mute from the word's end to the next word
-                    stop = probe.size(-1) if idx == len(words) - 1 else mid_end[idx + 1]
-                    probe[row, cut:stop] = 0
-                else:                                                    # mute from the previous word up to the start
-                    stop = 0 if idx == 0 else mid_start[idx - 1]
-                    probe[row, stop:cut] = 0
-            ref_p, ref_rank = self._probe(probe, text_tokens, word_tokens, rows, at_end)
-            track = np.zeros((ref_p.shape[-1], 3), dtype=np.int32)       # [failed once, passed once, last good boundary]
-            track[:, -1] = -1
-            first_cut = (mid_end, max_start) if at_end else (min_end, mid_start)
-            for idx, (s, e) in enumerate(zip(*first_cut)):
-                if not done[idx]:
-                    probe[idx % 2, s:e] = 0
-            prev_p = ref_p
-            while not np.all(done):
-                p, rank = self._probe(probe, text_tokens, word_tokens, rows, at_end)
-                abs_drop = ref_p - p
-                rel_drop = abs_drop / ref_p
-                step_drop = (prev_p - p) / prev_p
-                prev_p = p
-                for idx in range(len(words)):
-                    if done[idx]:
-                        continue
+                if at_end:
+                    lo, hi, mid = min_end[idx], max_end[idx], mid_end[idx]
+                else:
+                    lo, hi, mid = min_start[idx], max_start[idx], mid_start[idx]
+                row = rows[idx]
+                lost_rank = ref_rank[idx] > rank[idx]
+                failed = (abs_drop[idx] > self.abs_prob_decrease or rel_drop[idx] > self.rel_prob_decrease or
+                          (self.rel_rel_prob_decrease is not None and step_drop[idx] > self.rel_rel_prob_decrease) or
+                          p[idx] < self.prob_threshold or lost_rank)
+                if failed:
+                    track[idx][0] = 1
                     if at_end:
-                        lo, hi, mid = min_end[idx], max_end[idx], mid_end[idx]
+                        lo = mid
                     else:
-                        lo, hi, mid = min_start[idx], max_start[idx], mid_start[idx]
-                    row = rows[idx]
-                    lost_rank = ref_rank[idx] > rank[idx]
-                    failed = (abs_drop[idx] > self.abs_prob_decrease or rel_drop[idx] > self.rel_prob_decrease or
-                              (self.rel_rel_prob_decrease is not None and step_drop[idx] > self.rel_rel_prob_decrease) or
-                              p[idx] < self.prob_threshold or lost_rank)
-                    if failed:
-                        track[idx][0] = 1
-                        if at_end:
-                            lo = mid
-                        else:
-                            hi = mid
-                    else:
-                        track[idx][1] = 1
-                        if at_end:
-                            hi = mid
-                        else:
-                            lo = mid
-                    half = round((hi - lo) / 2)
-                    if half < self.sample_precision:
-                        done[idx] = True
-                        self._commit(idx, done, track, at_end, offset, words)
-                        continue
-                    new_mid = lo + half
-                    if failed:                                           # give audio back
-                        if at_end:
-                            probe[row, lo:new_mid] = clean[0, lo:new_mid]
-                        else:
-                            probe[row, new_mid:hi] = clean[0, new_mid:hi]
-                    elif at_end:                                         # mute more
-                        probe[row, new_mid:hi] = 0
-                    else:
-                        probe[row, lo:new_mid] = 0
+                        hi = mid
+                else:
+                    track[idx][1] = 1
                     if at_end:
-                        min_end[idx], max_end[idx], mid_end[idx] = lo, hi, new_mid
+                        hi = mid
                     else:
-                        min_start[idx], max_start[idx], mid_start[idx] = lo, hi, new_mid
-                    if not lost_rank:
-                        track[idx][-1] = new_mid
-                    ref_p[idx] = p[idx]
+                        lo = mid
+                half = round((hi - lo) / 2)
+                if half < self.sample_precision:
+                    done[idx] = True
+                    self._commit(idx, done, track, at_end, offset, words)
+                    continue
+                new_mid = lo + half
+                if failed:                                           # give audio back
+                    if at_end:
+                        probe[row, lo:new_mid] = clean[0, lo:new_mid]
+                    else:
+                        probe[row, new_mid:hi] = clean[0, new_mid:hi]
+                elif at_end:                                         # mute more
+                    probe[row, new_mid:hi] = 0
+                else:
+                    probe[row, lo:new_mid] = 0
+                if at_end:
+                    min_end[idx], max_end[idx], mid_end[idx] = lo, hi, new_mid
+                else:
+                    min_start[idx], max_start[idx], mid_start[idx] = lo, hi, new_mid
+                if not lost_rank:
+                    track[idx][-1] = new_mid
+                ref_p[idx] = p[idx]
