@@ -235,6 +235,20 @@ int swx_forward_logits(swx_model *m, const int32_t *d_tokens, const int32_t *h_n
 int swx_forward_token_ranks(swx_model *m, const int32_t *d_tokens, const int32_t *h_n_tok, int W, int max_n, int n_vocab_used,
                             const void *d_xkv, float *d_prob, int32_t *d_rank, void *stream);
 
+/* language identification on cross-K/V that is already resident (model.detect_language without the vocabulary projection):
+ * the teacher-forced pass of the single token `sot` for W windows -- the pass swx_forward_logits makes with max_n = 1, through
+ * the final LayerNorm, in the bound workspace -- then, per window, x_j = dot(hidden[w], E[d_lang_tokens[j]]) (f32 accumulation
+ * in both dtypes), softmax over the n_lang values and the arg-max (ties: the lowest j).
+ *  d_probs f32   [W][n_lang]   the probabilities, in the order of d_lang_tokens
+ *  d_best  int32 [W]           the token id of the most probable language
+ * Only enqueues: no allocation, no synchronisation, no [W][n_vocab] tensor; launch shapes depend on (W, n_lang, n_text_state),
+ * and a window's values do not depend on the batch it runs in.  Errors (nothing is launched): n_lang <= 0 or > n_vocab, `sot`
+ * outside the vocabulary, a null pointer (-1); W above the bound workspace's windows (-8).  The ids in d_lang_tokens are device
+ * memory: one outside [0, n_vocab) is never dereferenced and gets probability 0; callers check their list before uploading
+ * it. */
+int swx_detect_language(swx_model *m, const void *d_xkv, int W, int sot, const int32_t *d_lang_tokens, int n_lang,
+                        float *d_probs, int32_t *d_best, void *stream);
+
 /* ---- a7 stand-alone (test hook + extra_models path): weights f32 [W][H][N][ld_f] raw qk ->
  * neg_matrix f32 [W][N][1500].  d_scratch: swx_align_weights_scratch_bytes(W, H, N) bytes of device memory (no entry point of
  * this library allocates device memory) */

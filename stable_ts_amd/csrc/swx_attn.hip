@@ -1712,11 +1712,11 @@ int swx_attention(int dtype, const AttnArgs &a_in, int force_kernel, hipStream_t
         else hipLaunchKernelGGL((attn_flash2_f16<true, 2>), g, dim3(256), 0, s, a);
     } else if (dtype == SWX_F32 && (force_kernel == 0 || force_kernel == 7) && a.vt_kp % F32_KT == 0 &&
                // a transposed V is read as V[d][kt0 .. kt0 + 63] for every key tile: its row pitch must cover the padded key axis
-               (a.vt_kp == 0 || a.vt_kp >= cdiv(a.nk, F32_KT) * F32_KT) && f32_flash_ready(a.vt_kp != 0, a.nq <= 16)) {
+               (a.vt_kp == 0 || a.vt_kp >= cdiv(a.nk, F32_KT) * F32_KT) && f32_flash_ready(a.vt_kp != 0, a.nq <= 16 && !a.f32_no_split)) {
         // strict f32 on the exact-f32 matrix instruction: queries <= 16 per batch item (decode step: HBM-bound, the four waves split
         // the keys) or blocks of 128 queries (encoder self-attention, scoring pass: MFMA-bound).  Where the 68 KB of dynamic LDS
         // cannot be granted (f32_flash_ready: not gfx950) the launch falls through to the VALU kernel below.
-        const bool split = a.nq <= 16;
+        const bool split = a.nq <= 16 && !a.f32_no_split;
         SwxProfScope prof(split ? PC_ATTN_ROWWISE : PC_ATTN_FLASH,
                           split ? (double)a.B * a.H * 64 * esz * (2.0 * a.nk + 2.0 * a.nq) : 4.0 * a.B * a.H * (double)a.nq * a.nk * 64, s);
         dim3 gd(split ? 1 : cdiv(a.nq, 128), a.H, a.B);

@@ -182,6 +182,9 @@ struct AttnArgs {
     const _Float16 *fq_w; const float *fq_c1, *fq_c2; int fq_k;   // packed folded weights [d][fq_k], column constants
     const void *fq_pf; int fq_pf_lines;                     // weights to touch for the NEXT projection (cache prefetch), or null
     int fq_full_tile;                                       // A/B (SWX_FLAG_XQ_FULL_TILE): stage all 16 rows of the residual tile, not only the nq that exist
+    // strict f32: take the query-block kernel also at nq <= 16.  nq is the LONGEST window's token count in a multi-token pass: with
+    // the key-split kernel below 17 queries, a short window's numbers would depend on the windows it shares the pass with
+    int f32_no_split;
 };
 // fragment-ordered copy of one layer's cross K / V^T for the decode-step cross-attention: per (window, head)
 // [K: blocks of 32 keys x 4 fragments x 64 lanes x 8 halfs | V^T: the same], zero padded past nk

@@ -366,6 +366,7 @@ struct FwdCfg {
     int step_pos;          // decode step: position of the new token when the host knows it (profiler's byte count), else 0
     int pos_bound;         // decode step: upper bound of every row's position (initial tokens + sample budget), 0 = unknown
     unsigned char *qcap;   // non-null: the cross-attention queries of every layer are copied here, [L][rows][d] (swx_score_q)
+    bool xattn_by_blocks;  // strict f32: the cross-attention kernel must not depend on n_new (AttnArgs::f32_no_split)
 };
 
 // One decoder step (n_new == 1) in fp16: un-split "dec" GEMMs (swx_decstep.hip) that finish their own outputs.
@@ -593,6 +594,7 @@ int decoder_forward(swx_model *m, const FwdCfg &f, hipStream_t s)
         ca.q = qkv; ca.ldq = d; ca.k = kl; ca.v = kl + (size_t)D.n_audio_ctx * d * e; ca.ldkv = d;
         ca.k_bs = chunk; ca.v_bs = chunk; ca.vt_kp = SWX_VT_KP; ca.o = att; ca.ldo = d;
         ca.B = f.W; ca.H = H; ca.nq = f.rpw * f.n_new; ca.nk = D.n_audio_ctx; ca.q_rows_per_batch = f.rpw * f.n_new;
+        ca.f32_no_split = f.xattn_by_blocks ? 1 : 0;
         SWX_TRY(swx_attention(m->dtype, ca, 0, s));
         if (f.capture && !m->heads_by_layer[l].empty()) {
             SWX_TRY(swx_qk_capture(m->dtype, qkv, d, f.rpw * f.n_new, f.cap_row0, f.cap_rows, kl, d, chunk, D.n_audio_ctx,
@@ -719,6 +721,78 @@ __global__ void score_targets_kernel(const int32_t *__restrict__ tokens, int max
     const int w = idx / rows_per_w, i = idx % rows_per_w;
     const int p = n_sot + 1 + i;
     targets[idx] = (p < max_n) ? tokens[(size_t)w * max_n + p] : -1;
+}
+
+__global__ void fill_i32_kernel(int32_t *__restrict__ out, int32_t v, int n)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < n) out[idx] = v;
+}
+
+// Language identification (swx_detect_language): one workgroup per window.  hidden [W][d] = the final-LayerNorm'd state of the
+// <|sot|> row; wave k takes language tokens k, k + 4, ... and forms dot(hidden[w], E[tok_j]) over d: the embedding row in 16-byte
+// loads (VEC elements per lane), f32 products and sums in both dtypes, lane-sequential over the row and then the wave butterfly.
+// The softmax over the n_lang logits and the arg-max (ties -> the lowest index, as torch.argmax) stay in LDS.  Nothing here
+// depends on W, so a window's numbers are those of the same window alone.  A token id outside [0, V) is never dereferenced:
+// its logit is -inf (probability 0).  Dynamic LDS: (d + n_lang) floats.
+template <typename T>
+__global__ __launch_bounds__(256) void lang_id_kernel(const T *__restrict__ hidden, const T *__restrict__ E, int d, int V,
+                                                      const int32_t *__restrict__ lang_tokens, int n_lang,
+                                                      float *__restrict__ probs, int32_t *__restrict__ best)
+{
+    constexpr int VEC = 16 / (int)sizeof(T);
+    extern __shared__ float lang_sh[];
+    __shared__ float red[4];
+    __shared__ int best_j;
+    float *hs = lang_sh, *lg = lang_sh + d;
+    const int w = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const T *h = hidden + (size_t)w * d;
+    for (int i = tid; i < d; i += 256) hs[i] = to_f32<T>(h[i]);
+    if (tid == 0) best_j = n_lang;
+    __syncthreads();
+    for (int j = wave; j < n_lang; j += 4) {
+        const int tok = lang_tokens[j];
+        float acc = 0.f;
+        const bool ok = tok >= 0 && tok < V;
+        if (ok) {
+            const T *e = E + (size_t)tok * d;
+            for (int i = lane * VEC; i < d; i += 64 * VEC) {
+                if constexpr (VEC == 8) {
+                    const f16x8 v = *(const f16x8 *)(e + i);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) acc += hs[i + k] * (float)v[k];
+                } else {
+                    const f32x4 v = *(const f32x4 *)(e + i);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) acc += hs[i + k] * v[k];
+                }
+            }
+        }
+        acc = wave_sum(acc);
+        if (lane == 0) lg[j] = ok ? acc : -__builtin_inff();
+    }
+    __syncthreads();
+    float mx = -__builtin_inff();
+    for (int j = tid; j < n_lang; j += 256) mx = fmaxf(mx, lg[j]);
+    mx = wave_max(mx);
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float sum = 0.f;
+    for (int j = tid; j < n_lang; j += 256) {
+        const float x = lg[j];
+        if (x == mx) atomicMin(&best_j, j);
+        const float p = expf(x - mx);
+        lg[j] = p;
+        sum += p;
+    }
+    sum = wave_sum(sum);
+    if (lane == 0) red[wave] = sum;
+    __syncthreads();
+    sum = (red[0] + red[1]) + (red[2] + red[3]);
+    for (int j = tid; j < n_lang; j += 256) probs[(size_t)w * n_lang + j] = lg[j] / sum;
+    if (tid == 0) best[w] = best_j < n_lang ? lang_tokens[best_j] : -1;
 }
 
 }  // namespace
@@ -1473,6 +1547,10 @@ static int score_forward(swx_model *m, const int32_t *d_tokens, const int32_t *h
     f.anc = nullptr; f.xkv = (const unsigned char *)d_xkv;
     f.capture = capture;
     f.qcap = (unsigned char *)qcap;
+    // A teacher-forced pass over several tokens: max_n is the longest window's count, and a window of <= 16 tokens must get the
+    // numbers it gets next to a longer one (transcribe_many / transcribe_spans: windows of different recordings share the scoring
+    // pass).  A single-token pass (max_n == 1) is one query per window in any batch and keeps the key-split kernel.
+    f.xattn_by_blocks = max_n > 1;
     f.cap_row0 = cap_row0; f.cap_rows = cap_rows; f.cap_ld_n = cap_ld;
     if (capture && (cap_rows <= 0 || cap_row0 < 0 || cap_row0 + cap_rows > max_n || cap_ld < cap_rows)) return -1;
     return decoder_forward(m, f, s);
@@ -1613,6 +1691,42 @@ int swx_forward_token_ranks(swx_model *m, const int32_t *d_tokens, const int32_t
             SWX_CHECK_LAUNCH();
         }
     }
+    return 0;
+}
+
+// Language identification on features that are already resident: the teacher-forced pass of the single token `sot` (the pass
+// swx_forward_logits makes with max_n = 1, through the final LayerNorm) and lang_id_kernel over the n_lang language rows of the
+// embedding -- 0.2 % of the vocabulary projection, and W * (n_lang + 1) numbers out instead of [W][n_vocab] f32.  Enqueues only:
+// no allocation, no synchronisation; the launch shapes depend on (W, n_lang, d).  The token ids live on the device, so the
+// host cannot refuse one that is outside the vocabulary without waiting for the stream: the kernel never dereferences such
+// an id (probability 0), and the Python owner checks the list before it uploads it (Engine.detect_language).
+int swx_detect_language(swx_model *m, const void *d_xkv, int W, int sot, const int32_t *d_lang_tokens, int n_lang,
+                        float *d_probs, int32_t *d_best, void *stream)
+{
+    if (!m || !m->arena || !m->ws) return -9;
+    if (!d_xkv || !d_lang_tokens || !d_probs || !d_best) return -1;
+    const swx_dims &D = m->dims;
+    const int d = D.n_text_state;
+    if (n_lang <= 0 || n_lang > D.n_vocab || sot < 0 || sot >= D.n_vocab || W < 0) return -1;
+    if (W == 0) return 0;
+    if (W > m->max_windows || W > SMALL_I32) return -8;
+    const size_t lds = ((size_t)d + (size_t)n_lang) * sizeof(float);
+    if (d % 8 != 0 || lds > 48 * 1024) return -2;
+    hipStream_t s = S(stream);
+    int32_t *d_tok = m->Wp<int32_t>(m->L.small_i32);
+    hipLaunchKernelGGL(fill_i32_kernel, dim3(cdiv(W, 256)), dim3(256), 0, s, d_tok, (int32_t)sot, W);
+    SWX_CHECK_LAUNCH();
+    const std::vector<int32_t> ones((size_t)W, 1);
+    SWX_TRY(score_forward(m, d_tok, ones.data(), W, 1, 0, 0, 1, d_xkv, false, s));
+    unsigned char *x = m->ws + m->L.x, *hh = m->ws + m->L.h;
+    SWX_TRY(swx_layernorm(m->dtype, x, d, m->A<float>(m->o_ln_g), m->A<float>(m->o_ln_b), hh, d, W, d, s));
+    if (m->dtype == SWX_F16)
+        hipLaunchKernelGGL(lang_id_kernel<f16>, dim3(W), dim3(256), lds, s, (const f16 *)hh, (const f16 *)(m->arena + m->o_tok_emb), d,
+                           D.n_vocab, d_lang_tokens, n_lang, d_probs, d_best);
+    else
+        hipLaunchKernelGGL(lang_id_kernel<float>, dim3(W), dim3(256), lds, s, (const float *)hh, (const float *)(m->arena + m->o_tok_emb), d,
+                           D.n_vocab, d_lang_tokens, n_lang, d_probs, d_best);
+    SWX_CHECK_LAUNCH();
     return 0;
 }
 

@@ -50,6 +50,10 @@ class Engine:
     # decode() takes windows whose initial tokens differ in length as one lockstep job (swx_decode_cfg.sample_begins); the batch
     # drivers look for this attribute before they send such a job (decoding.use_ragged)
     ragged_decode = True
+    # detect_language() settles the language of windows whose cross-K/V is already resident (swx_detect_language: one decoder step
+    # + the language rows of the embedding); the lockstep driver of transcribe_many looks for this attribute and otherwise falls
+    # back to model.detect_language per recording
+    device_language_id = True
 
     def __init__(self, dims: ModelDimensions, dtype: str = "f16", device: str = "cuda:0",
                  max_windows: int = 1, max_rows: int = 5, alignment_heads: Optional[Sequence[Tuple[int, int]]] = None):
@@ -462,6 +466,23 @@ class Engine:
         check(self.lib.swx_forward_logits(self.h, _ptr(d_tok), _i32arr(n_tok), W, max_n, _ptr(xkv), _ptr(out),
                                           self.stream), "swx_forward_logits")
         return out
+
+    def detect_language(self, xkv: torch.Tensor, sot: int, lang_tokens: Sequence[int]) -> Tuple[np.ndarray, np.ndarray]:
+        """Language of every window in ``xkv`` (``swx_detect_language``): one decoder step at ``sot`` and the rows ``lang_tokens`` of
+        the embedding instead of the vocabulary projection.  Returns (best int32 [W] = the most probable language's token id,
+        probs f32 [W, n_lang] in the order of ``lang_tokens``), both on the host."""
+        W = int(xkv.n_windows)
+        toks = [int(t) for t in lang_tokens]
+        bad = [t for t in toks if not 0 <= t < self.dims.n_vocab]
+        if bad:       # the library cannot read the uploaded list back without waiting for the stream (swx.h)
+            raise IndexError(f"language token ids out of range for a vocabulary of {self.dims.n_vocab}: {bad[:8]}")
+        self.reserve(max(W, self.max_windows), max(self.max_rows, 1))
+        d_lang = torch.tensor(np.asarray(toks or [0], dtype=np.int32), device=self.device)
+        probs = torch.empty(W, max(len(toks), 1), dtype=torch.float32, device=self.device)
+        best = torch.empty(W, dtype=torch.int32, device=self.device)
+        check(self.lib.swx_detect_language(self.h, _ptr(xkv), W, int(sot), _ptr(d_lang), len(toks), _ptr(probs), _ptr(best),
+                                           self.stream), "swx_detect_language")
+        return best.cpu().numpy(), probs.cpu().numpy()
 
     def forward_token_ranks(self, xkv: torch.Tensor, tokens: Sequence[Sequence[int]], n_vocab_used: Optional[int] = None,
                             pad_token: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -305,7 +305,17 @@ def add_word_timestamps_batch(*, model, tokenizer, windows: Sequence[dict], xkv,
                               medfilt_width: int = 7, qk_scale: float = 1.0, dynamic_heads=None,
                               aligner: Union[str, dict] = "legacy", extra_models: Optional[list] = None, mel=None):
     """timing.py:411-500 for several windows at once.  windows[w] = dict(segments=[...], num_samples=int); the window
-    order matches the batch order inside `xkv`.  Mutates segments[i]['words'] / ['start'] / ['end'] in place."""
+    order matches the batch order inside `xkv`.  Mutates segments[i]['words'] / ['start'] / ['end'] in place.
+    ``tokenizer``: one for all windows, or a list with one per window (windows of recordings in different languages): the
+    window's own sot sequence goes into the scoring pass and its own language decides how words are split; the pass and the
+    DTW stay one device job."""
+    toks_w = list(tokenizer) if isinstance(tokenizer, (list, tuple)) else [tokenizer] * len(windows)
+    assert len(toks_w) == len(windows), "one tokenizer per window"
+    tokenizer = toks_w[0]
+    # what the job takes as ONE value must not depend on the language (special tokens sit at the same ids, sot sequences
+    # have the same length, the BPE ranks are shared)
+    assert all((len(t.sot_sequence), t.eot, t.no_timestamps) == (len(tokenizer.sot_sequence), tokenizer.eot, tokenizer.no_timestamps)
+               for t in toks_w[1:]), "tokenizers of one batch disagree on the special tokens"
     prepend_punctuations = PREPEND_PUNCTUATIONS if prepend_punctuations is None else prepend_punctuations
     append_punctuations = APPEND_PUNCTUATIONS if append_punctuations is None else append_punctuations
     min_word_dur = min_word_dur or 0
@@ -318,7 +328,7 @@ def add_word_timestamps_batch(*, model, tokenizer, windows: Sequence[dict], xkv,
             and not getattr(model, "missing_alignment_heads", False) and hasattr(eng, "score_start")):
         pad = None if gap_padding is None else (tokenizer.encode(gap_padding) if isinstance(gap_padding, str) else [gap_padding])
         toks, frames = [], []
-        for wd in windows:
+        for wd, tok_w in zip(windows, toks_w):
             flat = []
             for si, seg in enumerate(wd["segments"]):
                 text_only = [t for t in seg["tokens"] if not isinstance(t, int) or t < tokenizer.eot]
@@ -326,17 +336,17 @@ def add_word_timestamps_batch(*, model, tokenizer, windows: Sequence[dict], xkv,
                         and (pad_first_seg or si != 0)):
                     flat.extend(pad)
                 flat.extend(text_only)
-            toks.append([*tokenizer.sot_sequence, tokenizer.no_timestamps, *flat, tokenizer.eot])
+            toks.append([*tok_w.sot_sequence, tokenizer.no_timestamps, *flat, tokenizer.eot])
             frames.append(round(wd["num_samples"] / N_SAMPLES_PER_TOKEN))
         started = dict(tokens=toks, handle=eng.score_start(xkv, toks, frames, n_sot=len(tokenizer.sot_sequence),
                                                            eot=tokenizer.eot, qk_scale=qk_scale, medfilt_width=medfilt_width))
     jobs, seg_maps = [], []
-    for wd in windows:
+    for wd, tok_w in zip(windows, toks_w):
         for seg in wd["segments"]:
             seg["words"] = []
-        flat, token_split, seg_of_word = split_word_tokens(wd["segments"], tokenizer, padding=gap_padding,
+        flat, token_split, seg_of_word = split_word_tokens(wd["segments"], tok_w, padding=gap_padding,
                                                            split_callback=split_callback, pad_first_seg=pad_first_seg)
-        jobs.append(AlignmentJob(tokenizer, flat, wd["num_samples"], token_split))
+        jobs.append(AlignmentJob(tok_w, flat, wd["num_samples"], token_split))
         seg_maps.append(seg_of_word)
     if started is not None and started["tokens"] != [j.tokens for j in jobs]:
         started = None                         # cannot happen with the built-in splitter; a mismatch just costs a second pass

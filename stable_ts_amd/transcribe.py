@@ -11,6 +11,8 @@ Two drivers share one per-batch routine:
   * sequential (default): identical control flow to the reference, one window per iteration;
   * ``batch_size=N`` (window-parallel): fixed 30-s stride, no prompt carry-over, N windows per GPU batch -- the mode
     SURVEY.md 8e describes for throughput / sharding; its oracle is "the reference run on each 30-s clip separately".
+With several tracks the sequential driver advances them in lockstep, one window of each per device batch: the spans of one
+recording (spans.py) or different recordings with a language state each and slots that are refilled (many.py).
 Out of scope here: yt-dlp URLs, denoisers, VAD models, resume (non-WAVE containers need ffmpeg on PATH).
 """
 import time
@@ -85,12 +87,17 @@ def _xkv_select(model, xkv, idx: Sequence[int]):
 
 def _decode_with_fallback(model, xkv, base: dict, temperatures: Sequence[float], prompts, ts_masks,
                           compression_ratio_threshold, logprob_threshold, no_speech_threshold,
-                          uids: Optional[Sequence[int]] = None, torch_rng: bool = False) -> List[DecodingResult]:
+                          uids: Optional[Sequence[int]] = None, torch_rng: bool = False,
+                          languages: Optional[Sequence[str]] = None) -> List[DecodingResult]:
     """original_whisper.py:349-393, for W windows: every window walks the temperature ladder independently; the ones that
     still need a fallback are re-decoded together at the next temperature.  ``torch_rng`` (the sequential driver, one window
     per call): sampled retries draw from torch's generator call for call like the reference's loop (Engine.decode), so with
-    the same ``torch.manual_seed`` they are the reference's tokens; otherwise the draws are keyed on ``uids``."""
+    the same ``torch.manual_seed`` they are the reference's tokens; otherwise the draws are keyed on ``uids``.
+    ``languages``: one language per window (windows of different recordings in one job, transcribe_many); None = the
+    language of ``base`` for all of them."""
     W = xkv.n_windows
+    if languages is not None:
+        assert len(languages) == W, "one language per window"
     results: List[Optional[DecodingResult]] = [None] * W
     pending = list(range(W))
     for t in temperatures:
@@ -102,7 +109,8 @@ def _decode_with_fallback(model, xkv, base: dict, temperatures: Sequence[float],
             kw.pop("best_of", None)
         options = DecodingOptions(**kw, temperature=t)
         sub = _xkv_select(model, xkv, pending)
-        plans = [DecodingPlan(model, replace(options, prompt=(list(prompts[w]) if prompts[w] else None))) for w in pending]
+        plans = [DecodingPlan(model, replace(options, prompt=(list(prompts[w]) if prompts[w] else None),
+                                             **({} if languages is None else dict(language=languages[w])))) for w in pending]
         # one lockstep job for all pending windows, whatever the lengths of their prompts, on an engine that runs ragged jobs
         # (decoding.use_ragged); otherwise one job per distinct initial length
         ragged = use_ragged(model)
@@ -114,6 +122,14 @@ def _decode_with_fallback(model, xkv, base: dict, temperatures: Sequence[float],
         for _, ks in groups.items():
             sub_k = sub if len(ks) == len(pending) else _xkv_select(model, sub, ks)
             kw_e = plans[ks[0]].engine_kwargs()
+            if len({plans[k].options.language for k in ks}) > 1:
+                # windows of different languages share the job: the language lives in the initial tokens alone -- the suppress
+                # list and every other argument of the job are the same for all of them (checked, not assumed)
+                same = {k_: v for k_, v in kw_e.items() if k_ != "sot_index"}
+                for k in ks[1:]:
+                    other = plans[k].engine_kwargs()
+                    other.pop("sot_index")
+                    assert other == same, "decode arguments depend on the language"
             if len({(plans[k].sample_begin, plans[k].sot_index) for k in ks}) > 1:
                 kw_e["sot_index"] = [plans[k].sot_index for k in ks]
             masks = None
@@ -124,7 +140,7 @@ def _decode_with_fallback(model, xkv, base: dict, temperatures: Sequence[float],
                                       window_uid=None if uids is None else [uids[pending[k]] for k in ks],
                                       **(dict(torch_rng=True) if torch_rng and t > 0 and W == 1 else {}),
                                       **kw_e)
-            for k, r in zip(ks, plans[ks[0]].results(out, [None] * len(ks), [options.language or "en"] * len(ks))):
+            for k, r in zip(ks, plans[ks[0]].results(out, [None] * len(ks), [plans[k].options.language or "en" for k in ks])):
                 outs[k] = r
         nxt = []
         for k, w in enumerate(pending):
@@ -205,8 +221,15 @@ def _start_encoder(model, audios: List[torch.Tensor]) -> dict:
 def _process_batch(model, tokenizer, batch: List[dict], o: dict, pre: Optional[dict] = None) -> List[dict]:
     """Runs the hot path for a batch of windows.  batch[w] = dict(audio=1-D f32 tensor (<=480000), seek_sample=int,
     prompt=list[int], ts_mask=bool[1501] | None).  Returns per window dict(segments, segment_samples, result, skipped).
-    ``pre``: what `_start_encoder` enqueued earlier for (a superset of) these windows."""
+    ``pre``: what `_start_encoder` enqueued earlier for (a superset of) these windows.
+    ``tokenizer``: one for the batch, or a list with one per window (windows of different recordings, transcribe_many); the
+    windows then also carry their ``language``."""
     W = len(batch)
+    toks = list(tokenizer) if isinstance(tokenizer, (list, tuple)) else [tokenizer] * W
+    assert len(toks) == W, "one tokenizer per window"
+    languages = [b.get("language") for b in batch]
+    if all(l is None for l in languages):
+        languages = None
     audios = [b["audio"] for b in batch]
     seg_samples = [int(a.shape[-1]) for a in audios]
     import time
@@ -232,7 +255,7 @@ def _process_batch(model, tokenizer, batch: List[dict], o: dict, pre: Optional[d
     results = _decode_with_fallback(model, xkv, o["decode_options"], o["temperatures"], [b["prompt"] for b in batch],
                                     ts_masks, o["compression_ratio_threshold"], o["logprob_threshold"],
                                     o["no_speech_threshold"], uids=[int(b["seek_sample"]) // 160 for b in batch],
-                                    torch_rng=bool(o.get("torch_sampling")))
+                                    torch_rng=bool(o.get("torch_sampling")), languages=languages)
     t_ph = _phase("decode (device loop + result copy)", t_ph)
     time_precision = (N_FRAMES // model.dims.n_audio_ctx) * HOP_LENGTH / SAMPLE_RATE
     punct = o["prepend_punctuations"] + o["append_punctuations"]
@@ -254,7 +277,7 @@ def _process_batch(model, tokenizer, batch: List[dict], o: dict, pre: Optional[d
             continue
         time_offset = batch[w]["seek_sample"] / SAMPLE_RATE
         seg_dur = seg_samples[w] / SAMPLE_RATE
-        segs, single_end, end_ts_pos = _slice_segments(r.tokens, r, tokenizer, time_offset, batch[w]["seek_sample"],
+        segs, single_end, end_ts_pos = _slice_segments(r.tokens, r, toks[w], time_offset, batch[w]["seek_sample"],
                                                        seg_dur, time_precision)
         for i in reversed(range(len(segs))):                                                    # :604-627
             s = segs[i]
@@ -281,7 +304,7 @@ def _process_batch(model, tokenizer, batch: List[dict], o: dict, pre: Optional[d
         idx = [w for w in range(W) if outs[w]["segments"]]
         if idx:
             add_word_timestamps_batch(                                                          # :635-652
-                model=model, tokenizer=tokenizer,
+                model=model, tokenizer=tokenizer if not isinstance(tokenizer, (list, tuple)) else [toks[w] for w in idx],
                 windows=[dict(segments=outs[w]["segments"], num_samples=outs[w]["num_samples"]) for w in idx],
                 xkv=_xkv_select(model, xkv, idx), prepend_punctuations=o["prepend_punctuations"],
                 append_punctuations=o["append_punctuations"],     # min_word_dur stays at the callee's 0.1 (:636-652)
@@ -333,7 +356,7 @@ def transcribe_stable(model, audio, *, verbose: Optional[bool] = False,
                       only_ffmpeg: bool = False, denoiser: Optional[str] = None, denoiser_options: Optional[dict] = None,
                       extra_models: Optional[list] = None, dynamic_heads: Optional[Union[bool, int, str]] = None,
                       aligner: Union[str, dict] = "legacy", _span_bounds: Optional[List[Tuple[int, int]]] = None,
-                      **decode_options) -> WhisperResult:
+                      _many: Optional[dict] = None, **decode_options) -> WhisperResult:
     """Same keyword surface as the reference's ``model.transcribe`` for the options that reach the hot path
     (original_whisper.py:27-79); ``batch_size`` (window-parallel mode) and ``streams`` are the only additions.
     ``audio``: waveform (tensor / array, 16 kHz), file path or file bytes, or an ``AudioLoader``; ``stream`` loads files
@@ -359,47 +382,78 @@ def transcribe_stable(model, audio, *, verbose: Optional[bool] = False,
         sections = [list(clip_timestamps[i:i + 2]) for i in range(0, len(clip_timestamps), 2)]
         if len(sections[-1]) == 1:
             sections[-1] = [sections[-1][0], None]
-    if isinstance(audio, AudioLoader):                                                          # :289-298
-        audio.validate_external_args(sr=SAMPLE_RATE, vad=vad, stream=stream, denoiser=denoiser,
-                                     denoiser_options=denoiser_options, only_voice_freq=only_voice_freq)
-        audio.load_sections = sections
-        loader = audio
-    else:                                                                                       # :299-311
-        if torch.is_tensor(audio) or isinstance(audio, np.ndarray):
+
+    def open_loader(audio) -> AudioLoader:
+        if isinstance(audio, AudioLoader):                                                      # :289-298
+            audio.validate_external_args(sr=SAMPLE_RATE, vad=vad, stream=stream, denoiser=denoiser,
+                                         denoiser_options=denoiser_options, only_voice_freq=only_voice_freq)
+            audio.load_sections = sections
+            return audio
+        if torch.is_tensor(audio) or isinstance(audio, np.ndarray):                             # :299-311
             audio = as_waveform(audio)
-        loader = AudioLoader(audio, stream=stream, denoiser=denoiser, denoiser_options=denoiser_options,
-                             only_voice_freq=only_voice_freq, only_ffmpeg=only_ffmpeg, verbose=verbose,
-                             new_chunk_divisor=None, load_sections=sections)
+        return AudioLoader(audio, stream=stream, denoiser=denoiser, denoiser_options=denoiser_options,
+                           only_voice_freq=only_voice_freq, only_ffmpeg=only_ffmpeg, verbose=verbose,
+                           new_chunk_divisor=None, load_sections=sections)
+
+    # ``_many`` (transcribe_many): the recordings are opened one by one as they take a slot of the lockstep driver
+    loader = None if _many is not None else open_loader(audio)
 
     # Language and tokenizer are settled at the FIRST WINDOW THAT IS ACTUALLY DECODED (original_whisper.py:319-345, called at
     # :532 after the silent windows were skipped, after nonspeech_skip trimmed the window and inside the first clip section) --
     # not on the first 30 s of the file.  `settle_language` is called with that window's audio right before its batch runs.
-    lang_state = dict(language=decode_options.get("language"), tokenizer=None, prompt_tokens=[])
-    if lang_state["language"] or not model.is_multilingual:
-        lang_state["language"] = lang_state["language"] or "en"
+    # The language state (language, tokenizer, initial-prompt tokens) belongs to a track.  The tracks of ONE recording (the plain
+    # run, the spans of transcribe_spans) share one state object; the recordings of transcribe_many have one each.
+    def new_lang_state(language: Optional[str]) -> dict:
+        st = dict(language=language, tokenizer=None, prompt_tokens=[])
+        if st["language"] or not model.is_multilingual:
+            st["language"] = st["language"] or "en"
+            st["tokenizer"] = get_tokenizer(model.is_multilingual, num_languages=model.num_languages,
+                                            language=st["language"], task=task)
+            if initial_prompt is not None:                                                      # :342-345
+                st["prompt_tokens"] = st["tokenizer"].encode(" " + initial_prompt.strip())
+        return st
+
+    lang_state = new_lang_state(decode_options.get("language"))
+    if lang_state["tokenizer"] is not None and _many is None:
         decode_options["language"] = lang_state["language"]
-        lang_state["tokenizer"] = get_tokenizer(model.is_multilingual, num_languages=model.num_languages,
-                                                language=lang_state["language"], task=task)
-        if initial_prompt is not None:                                                          # :342-345
-            lang_state["prompt_tokens"] = lang_state["tokenizer"].encode(" " + initial_prompt.strip())
     initial_prompt_tokens: List[int] = lang_state["prompt_tokens"]
 
-    def settle_language(first_audio: torch.Tensor, tracks_: list):
-        if lang_state["tokenizer"] is not None:
+    def set_language(st: dict, lang: str, tracks_: list):
+        """the language of ``st`` is now known: tokenizer, initial prompt, and the prompt history of the tracks that share ``st``"""
+        st["language"] = lang
+        if st is lang_state and _many is None:
+            decode_options["language"] = lang
+        tok = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=lang, task=task)
+        st["tokenizer"] = tok
+        if initial_prompt is not None:
+            st["prompt_tokens"].extend(tok.encode(" " + initial_prompt.strip()))
+            for tr in tracks_:                      # the reference extends all_tokens at this point (:344-345)
+                if tr.lang is st:
+                    tr.all_tokens.extend(st["prompt_tokens"])
+
+    def settle_language(first_audio: torch.Tensor, tracks_: list, st: Optional[dict] = None):
+        st = lang_state if st is None else st
+        if st["tokenizer"] is not None:
             return
         n = int(first_audio.shape[-1])
         mel0 = model.log_mel(first_audio, max(N_SAMPLES - n, 0))
         _, probs = model.detect_language(mel0)
-        lang = max(probs, key=probs.get)
-        lang_state["language"] = decode_options["language"] = lang
-        tok = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=lang, task=task)
-        lang_state["tokenizer"] = tok
-        if initial_prompt is not None:
-            lang_state["prompt_tokens"].extend(tok.encode(" " + initial_prompt.strip()))
-            for tr in tracks_:                      # the reference extends all_tokens at this point (:344-345)
-                tr.all_tokens.extend(lang_state["prompt_tokens"])
+        set_language(st, max(probs, key=probs.get), tracks_)
 
-    def new_track(source: AudioLoader, offset: int = 0) -> _Track:
+    def settle_languages_on_device(items_: list, todo: List[int]) -> dict:
+        """transcribe_many on an engine with ``device_language_id``: the round's spectrogram, encoder and cross-K/V are started
+        ONCE; the windows in ``todo`` (first live window of a recording whose language is unknown) get their language from one
+        decoder step on those features (Engine.detect_language); `_process_batch` then picks the same features up."""
+        pre = _start_encoder(model, [it["audio"] for _, it in items_])
+        any_tok = get_tokenizer(model.is_multilingual, num_languages=model.num_languages)
+        lang_tokens, codes = list(any_tok.all_language_tokens), list(any_tok.all_language_codes)
+        best, _ = model.engine.detect_language(_xkv_select(model, pre["xkv"], todo), any_tok.sot, lang_tokens)
+        for k, b in zip(todo, best.tolist()):
+            tr = items_[k][0]
+            set_language(tr.lang, codes[lang_tokens.index(int(b))], [tr])
+        return pre
+
+    def new_track(source: AudioLoader, offset: int = 0, lang: Optional[dict] = None) -> _Track:
         from .stabilization import NonSpeechPredictor
         # :427-441: one predictor per run, always (an all-zero window is fast-forwarded in every mode); the
         # loudness-based detector only with suppress_silence, otherwise it looks at exact-zero samples and yields no
@@ -407,16 +461,19 @@ def transcribe_stable(model, audio, *, verbose: Optional[bool] = False,
         predictor = NonSpeechPredictor(q_levels=q_levels, k_size=k_size, min_word_dur=min_word_dur,
                                        min_silence_dur=min_silence_dur, get_mask=suppress_ts_tokens,
                                        loudness=bool(suppress_silence))
-        return _Track(source, predictor, list(initial_prompt_tokens), offset)
+        lang = lang_state if lang is None else lang
+        return _Track(source, predictor, list(lang["prompt_tokens"]), offset, lang)
 
     # one track = one run of the reference's sequential algorithm; ``_span_bounds`` (transcribe_spans) makes several
-    if _span_bounds:
+    if _many is not None:
+        tracks = []                 # filled as recordings take their slots
+    elif _span_bounds:
         whole = loader.next_chunk(0, loader.get_total_samples())
         tracks = [new_track(AudioLoader(whole[a0:b0], new_chunk_divisor=None), a0) for a0, b0 in _span_bounds]
     else:
         tracks = [new_track(loader)]
-    tr0 = tracks[0]
-    nonspeech = tr0.nonspeech
+    tr0 = tracks[0] if tracks else None
+    nonspeech = tr0.nonspeech if tr0 is not None else None
 
     o = dict(decode_options=decode_options,
              temperatures=[temperature] if isinstance(temperature, (int, float)) else list(temperature),
@@ -429,7 +486,7 @@ def transcribe_stable(model, audio, *, verbose: Optional[bool] = False,
              suppress_ts_tokens=suppress_ts_tokens, extra_models=extra_models, dynamic_heads=dynamic_heads, aligner=aligner,
              # the reference's own control flow (one track, one window per decode call) samples from torch's generator like the
              # reference; window-parallel / span modes decode several windows per call and key the draws on the window instead
-             torch_sampling=not batch_size and not _span_bounds)
+             torch_sampling=not batch_size and not _span_bounds and _many is None)
 
     def host_copy(seg: torch.Tensor) -> torch.Tensor:
         return seg.detach().float().cpu()                       # silence analysis is host-side vector code (CPU)
@@ -465,6 +522,8 @@ def transcribe_stable(model, audio, *, verbose: Optional[bool] = False,
 
     def window_input(tr: _Track, seek: int, seg: torch.Tensor, prompt: List[int], pred: Optional[dict] = None):
         item = dict(audio=seg, seek_sample=seek, prompt=prompt, ts_mask=None, silence=None, skip=False)
+        if _many is not None:
+            item["language"] = tr.lang["language"]      # per window through the hot path; None until the track's language is settled
         if tr.nonspeech is not None:
             if pred is None:
                 pred = predict_nonspeech(tr.nonspeech, [seg], [seek / SAMPLE_RATE])[0]
@@ -620,32 +679,86 @@ def transcribe_stable(model, audio, *, verbose: Optional[bool] = False,
     else:
         # ---- sequential driver (reference control flow); with several tracks the tracks advance in lockstep, one window
         # of each per device batch -- every track still sees exactly the reference's sequence of windows and prompts
+        # ``_many``: the tracks are different recordings, each with its own language state; at most ``max_tracks`` are live, and
+        # the next pending recording takes the slot of one that ran out of audio in the following round
         active = list(tracks)
-        while active:
+        pending = list(range(len(_many["audios"]))) if _many is not None else []
+        pending.reverse()                               # pop() hands them out in input order
+        device_lang = _many is not None and bool(getattr(model.engine, "device_language_id", False))
+        many_total = many_done = 0
+        if _many is not None and progress_callback is not None:
+            many_total = sum(_source_samples(a) for a in _many["audios"])
+
+        def open_next() -> _Track:
+            i = pending.pop()
             try:
-                items = [(tr, it) for tr in active if (it := next_live_item(tr)) is not None]
+                source = open_loader(_many["audios"][i])
+            except Exception as e:                      # what transcribe() raises for this recording, with its place in the list
+                raise _with_index(e, i) from e
+            tr = new_track(source, lang=new_lang_state(_many["languages"][i]))
+            tr.index = i
+            tracks.append(tr)
+            return tr
+
+        while active or pending:
+            try:
+                while pending and len(active) < _many["max_tracks"]:
+                    active.append(open_next())
+                items, ended = [], []
+                for tr in active:
+                    it = next_live_item(tr)
+                    (items if it is not None else ended).append((tr, it))
+                for tr, _ in ended:
+                    if _many is not None:
+                        many_done += tr.loader.get_total_samples()
+                        tr.loader.terminate()
+                    tr.finished = True
                 if not items:
+                    if pending:
+                        active = []
+                        continue
                     break
-                if lang_state["tokenizer"] is None:
-                    settle_language(items[0][1]["audio"], tracks)
+                pre = None
+                todo = [k for k, (tr, _) in enumerate(items) if tr.lang["tokenizer"] is None]
+                if todo:
+                    if device_lang:
+                        pre = settle_languages_on_device(items, todo)
+                    else:
+                        for k in todo:                  # tracks that share a state settle it once: on the first of them
+                            settle_language(items[k][1]["audio"], tracks, items[k][0].lang)
                     for tr, it in items:                # the prompt slices were taken before the initial prompt was known
                         it["prompt"] = tr.all_tokens[tr.prompt_reset_since:]
-                outs = _process_batch(model, lang_state["tokenizer"], [it for _, it in items], o)
+                        if _many is not None:
+                            it["language"] = tr.lang["language"]
+                toks = [tr.lang["tokenizer"] for tr, _ in items]
+                outs = _process_batch(model, toks[0] if all(t is toks[0] for t in toks) else toks, [it for _, it in items], o,
+                                      pre=pre)
             except KeyboardInterrupt:                                                           # :716-723
-                interrupted.append(_interrupted_time(tracks[0], tracks[0].seek))
+                if _many is not None:
+                    for tr in active:
+                        if not tr.finished:
+                            tr.unfinished_start = _interrupted_time(tr, tr.seek)
+                else:
+                    interrupted.append(_interrupted_time(tracks[0], tracks[0].seek))
                 break
             for (tr, it), out in zip(items, outs):
                 advance(tr, it, out)
             active = [tr for tr, _ in items]
             if progress_callback is not None:
-                total = loader.get_total_samples()
-                at = sum(min(tr.seek, tr.loader.get_total_samples()) for tr in tracks)
-                progress_callback(min(at, total) / SAMPLE_RATE, total / SAMPLE_RATE)
-    loader.terminate()                                                                          # :731
+                if _many is not None:
+                    at = many_done + sum(min(tr.seek, tr.loader.get_total_samples()) for tr in active)
+                    progress_callback(min(at, many_total) / SAMPLE_RATE, many_total / SAMPLE_RATE)
+                else:
+                    total = loader.get_total_samples()
+                    at = sum(min(tr.seek, tr.loader.get_total_samples()) for tr in tracks)
+                    progress_callback(min(at, total) / SAMPLE_RATE, total / SAMPLE_RATE)
+    if loader is not None:
+        loader.terminate()                                                                      # :731
 
     def finish(tr: _Track) -> WhisperResult:
-        language = lang_state["language"]
-        tokenizer = lang_state["tokenizer"]
+        language = tr.lang["language"]
+        tokenizer = tr.lang["tokenizer"]
+        initial_prompt_tokens = tr.lang["prompt_tokens"]
         if tokenizer is None:       # nothing was ever decoded (all windows silent): no language was settled (:527)
             tokenizer = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language="en", task=task)
         text = tokenizer.decode(tr.all_tokens[len(initial_prompt_tokens):])
@@ -661,6 +774,19 @@ def transcribe_stable(model, audio, *, verbose: Optional[bool] = False,
             regroup_default(result, regroup)
         return result
 
+    if _many is not None:
+        results: List[Optional[WhisperResult]] = [None] * len(_many["audios"])
+        for tr in tracks:
+            tr.loader.terminate()
+            res = results[tr.index] = finish(tr)
+            if tr.unfinished_start is not None:
+                res.unfinished_start = tr.unfinished_start
+            if len(res.text) == 0:
+                warnings.warn(f"Failed to {task} audio {tr.index}. Result contains no text. ")
+        for i in pending:                               # interrupted before these were opened: nothing of them is done
+            res = results[i] = WhisperResult(dict(text="", segments=[], language=None, time_scale=None))
+            res.unfinished_start = 0.0
+        return results
     if _span_bounds:
         return [(tr.offset, finish(tr)) for tr in tracks]
     t_ph = time.perf_counter() if PHASE_TIMES is not None else 0.0
@@ -712,12 +838,39 @@ def transcribe_minimal(model, audio, *, verbose: Optional[bool] = False, word_ti
                           force_order=True, **extra)
 
 
-class _Track:
-    """State of one run of the reference's sequential window loop (seek, prompt history, segments, silence analysis)."""
-    __slots__ = ("loader", "nonspeech", "all_tokens", "all_segments", "prompt_reset_since", "seek", "offset", "started")
+def _source_samples(audio) -> int:
+    """length in 16 kHz samples of something ``transcribe`` accepts, without decoding it (progress totals)"""
+    if isinstance(audio, AudioLoader):
+        return int(audio.get_total_samples())
+    if torch.is_tensor(audio) or isinstance(audio, np.ndarray):
+        return int(audio.shape[-1])
+    from .audio_io import get_metadata
+    try:
+        return round((get_metadata(audio)["duration"] or 0) * SAMPLE_RATE)
+    except Exception:
+        return 0
 
-    def __init__(self, loader: AudioLoader, nonspeech, prompt_tokens: List[int], offset: int = 0):
+
+def _with_index(e: Exception, i: int) -> Exception:
+    """the same kind of exception with the recording's index in front of the message"""
+    try:
+        return type(e)(f"audios[{i}]: {e}")
+    except Exception:
+        return RuntimeError(f"audios[{i}]: {e}")
+
+
+class _Track:
+    """State of one run of the reference's sequential window loop (seek, prompt history, segments, silence analysis) and the
+    language state it decodes with (shared between the tracks of one recording)."""
+    __slots__ = ("loader", "nonspeech", "all_tokens", "all_segments", "prompt_reset_since", "seek", "offset", "started", "lang",
+                 "index", "finished", "unfinished_start")
+
+    def __init__(self, loader: AudioLoader, nonspeech, prompt_tokens: List[int], offset: int = 0, lang: Optional[dict] = None):
         self.loader, self.nonspeech, self.all_tokens, self.offset = loader, nonspeech, prompt_tokens, offset
+        self.lang = lang
+        self.index = 0
+        self.finished = False
+        self.unfinished_start: Optional[float] = None
         self.all_segments: List[dict] = []
         self.prompt_reset_since = 0
         self.seek = 0
