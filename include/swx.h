@@ -361,6 +361,26 @@ int swx_test_lane_xor(const uint32_t *d_in, uint32_t *d_out, int n_waves, void *
  * results whose payloads differ.  Nothing in the reference corresponds to it. */
 int swx_test_gelu_pair(uint64_t *d_out, void *stream);
 
+/* the selection path of swx_decode on the CALLER'S logits (csrc/swx_decode.hip: the logit filters, token selection, beam update,
+ * step finish and finalize kernels), with no model and no forward pass: swx_decode_init, swx_decode_after_prefill on
+ * d_prefill_logits, then per step [copy the step's slice of the script into the logits rows -> selection of token i] launched
+ * eagerly, and finalize.  The loop ends by the conditions of swx_decode (one shared host function): context full, every window
+ * done (polled every 8 steps once min_tokens have been sampled), sample_len used up.  n_vocab and n_ctx are free (the token
+ * buffers are n_ctx + 1 wide); cfg is read as by swx_decode (sample_begins: a ragged job; sot_index / sot_indices / window_uid are
+ * not used; noise: DEVICE [sample_len][W * G][n_vocab]); debug flag 8192 selects the memory-walking kernel as in swx_decode.
+ *  d_init_tokens int32 [W][longest window]; d_suppress int32 [n_suppress] or NULL; d_ts_mask uint8 [W][1501] or NULL
+ *  d_prefill_logits f32 [W][2][n_vocab]  row 0: the SOT position (no-speech probability), row 1: the logits token 0 is selected from
+ *  d_script f32 [n_script][W * G][n_vocab]  slice i - 1: the logits token i is selected from ("size out of range" when the loop
+ *           needs a slice past n_script)
+ *  outputs as swx_decode's (d_nospeech may be NULL), and, both optional: d_anc_out int32 [W * G][n_ctx], the final ancestor table
+ *  (written when G > 1), d_pos0_out int32 [W * G].  d_ws: swx_test_decode_script_ws_bytes(cfg, n_vocab, n_ctx) bytes of device
+ *  memory, 256-byte aligned.  Returns the number of steps executed or a negative error; blocks until the loop has finished. */
+size_t swx_test_decode_script_ws_bytes(const swx_decode_cfg *cfg, int n_vocab, int n_ctx);
+int swx_test_decode_script(const swx_decode_cfg *cfg, int n_vocab, int n_ctx, const int32_t *d_init_tokens,
+                           const int32_t *d_suppress, const uint8_t *d_ts_mask, const float *d_prefill_logits,
+                           const float *d_script, int n_script, int32_t *d_tokens_out, int32_t *d_lens_out, float *d_sumlp_out,
+                           float *d_nospeech, int32_t *d_anc_out, int32_t *d_pos0_out, void *d_ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

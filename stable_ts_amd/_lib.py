@@ -105,6 +105,10 @@ SYMBOLS = {
                                         c_void_p]),
     "swx_test_self_attn_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "swx_test_gelu_pair": (c_int, [c_void_p, c_void_p]),
+    "swx_test_decode_script_ws_bytes": (c_size_t, [POINTER(swx_decode_cfg), c_int, c_int]),
+    "swx_test_decode_script": (c_int, [POINTER(swx_decode_cfg), c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                       c_void_p]),
     "swx_test_lane_xor": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "swx_test_layernorm": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "swx_test_attention": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int,

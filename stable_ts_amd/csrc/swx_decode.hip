@@ -227,7 +227,9 @@ __global__ __launch_bounds__(SEL_T) void decode_select_kernel(DecodeBufs b, int 
         for (int i = tid; i < V; i += SEL_T) {
             float v = lg[i];
             if ((i >= lo0 && i < hi0) || (i >= tsb && i < hi1) || (i < hi2) || (i >= lo3)) { v = NEG_INF; lg[i] = v; }
-            if (i < tsb) mx_text = fmaxf(mx_text, v); else mx_ts = fmaxf(mx_ts, v);
+            // (a NaN text logit counts as +inf here: upstream compares log-softmax values of the WHOLE row, which are all NaN then,
+            //  and leaves the text tokens alone; v_max_f32 would drop the NaN.  A NaN among the timestamps makes lse_ts NaN: the same)
+            if (i < tsb) mx_text = fmaxf(mx_text, v != v ? -NEG_INF : v); else mx_ts = fmaxf(mx_ts, v);
         }
         mx_text = block_max(mx_text, shf);
         mx_ts = block_max(mx_ts, shf);
@@ -368,7 +370,7 @@ __global__ __launch_bounds__(SEL_T) void decode_select_reg_kernel(DecodeBufs b, 
             const int i = tid + k * SEL_T;
             if (i < V) {
                 if ((i >= lo0 && i < hi0) || (i >= tsb && i < hi1) || (i < hi2) || (i >= lo3)) v[k] = NEG_INF;
-                if (i < tsb) mx_text = fmaxf(mx_text, v[k]); else mx_ts = fmaxf(mx_ts, v[k]);
+                if (i < tsb) mx_text = fmaxf(mx_text, v[k] != v[k] ? -NEG_INF : v[k]); else mx_ts = fmaxf(mx_ts, v[k]);   // (NaN: as above)
             }
         }
         mx_text = block_max(mx_text, shf);

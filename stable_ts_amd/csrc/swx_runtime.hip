@@ -1267,6 +1267,28 @@ __global__ __launch_bounds__(64) void gather_rows_kernel(const unsigned char *__
     uint4 *dp = (uint4 *)(dst + (size_t)j * row_bytes);
     for (int i = threadIdx.x; i < row_bytes / 16; i += 64) dp[i] = sp[i];
 }
+
+// The exit conditions of the decode loop, looked at after the selection of token i (swx_decode and swx_test_decode_script: one
+// function so that the two loops cannot drift apart).  Returns 1 when the loop ends, 0 when it goes on, < 0 on a HIP error.
+//  * tokens.shape[-1] > n_ctx (decode.py:60).  n_min = the shortest window's initial tokens: in a ragged job a longer window met
+//    this earlier and was frozen on the device (decode_step_finish_kernel); the job ends when the shortest window meets it
+//  * every window done: one host sync every DECODE_POLL steps, pointless while EOT is still suppressed by min_tokens
+//  * the budget sample_len used up
+constexpr int DECODE_POLL = 8;
+int decode_loop_stop(int i, int n_min, int n_ctx, int min_tokens, int sample_len, int W, const int32_t *d_n_done, hipStream_t s)
+{
+    const int steps = i + 1;
+    if (n_min + i + 1 > n_ctx) return 1;
+    if ((steps % DECODE_POLL == 0 && steps >= min_tokens) || steps == sample_len) {
+        int32_t h_done = 0;
+        hipError_t er = hipMemcpyAsync(&h_done, d_n_done, 4, hipMemcpyDeviceToHost, s);
+        if (er != hipSuccess) return -100 - (int)er;
+        er = hipStreamSynchronize(s);
+        if (er != hipSuccess) return -100 - (int)er;
+        if (h_done >= W) return 1;
+    }
+    return steps >= sample_len ? 1 : 0;
+}
 }  // namespace
 
 int swx_decode_gout(const swx_decode_cfg *cfg)
@@ -1440,11 +1462,9 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
     SWX_TRY(swx_decode_after_prefill(b, lg2, d_nospeech, s));
 
     int cur = 0, steps = 0;
-    int32_t h_done = 0;
-    const int CHECK = 8;
     // One unit of the loop = [forward pass of the rows' newest tokens -> final LayerNorm -> logits] + [selection of token i].
     // Token 0 is selected from the prefill logits; after every selection the loop's exit conditions are looked at:
-    // context full (decode.py:60), every window done (one host sync every CHECK steps), budget used up.
+    // context full (decode.py:60), every window done (one host sync every DECODE_POLL steps), budget used up: decode_loop_stop.
     auto unit = [&](int cur_in, hipStream_t st, bool capturing = false) -> int {
         FwdCfg g{};
         g.W = W; g.rpw = G; g.row_mul = 1; g.n_new = 1;
@@ -1470,18 +1490,7 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
     // returns 1 when the loop ends after the selection of token i
     auto after_select = [&](int i) -> int {
         steps = i + 1;
-        // tokens.shape[-1] > n_ctx (decode.py:60).  Ragged job: a longer window met this earlier and was frozen on the device
-        // (decode_step_finish_kernel); the job ends when the shortest window meets it
-        if (n_min + i + 1 > D.n_text_ctx) return 1;
-        // early-exit poll (one host sync); pointless while EOT is still suppressed by min_tokens
-        if ((steps % CHECK == 0 && steps >= cfg->min_tokens) || steps == cfg->sample_len) {
-            er = hipMemcpyAsync(&h_done, b.n_done, 4, hipMemcpyDeviceToHost, s);
-            if (er != hipSuccess) return -100 - (int)er;
-            er = hipStreamSynchronize(s);
-            if (er != hipSuccess) return -100 - (int)er;
-            if (h_done >= W) return 1;
-        }
-        return i + 1 >= cfg->sample_len ? 1 : 0;
+        return decode_loop_stop(i, n_min, D.n_text_ctx, cfg->min_tokens, cfg->sample_len, W, b.n_done, s);
     };
     SWX_TRY(swx_decode_select(b, cur, s));
     if (cfg->beam) cur ^= 1;
@@ -1969,6 +1978,139 @@ int swx_test_gelu_pair(uint64_t *d_out, void *stream)
     hipLaunchKernelGGL(gelu_pair_check_kernel, dim3(1u << 19), dim3(256), 0, s, (unsigned long long *)d_out);
     SWX_CHECK_LAUNCH();
     return 0;
+}
+
+// ---- swx_test_decode_script: the selection path of swx_decode on the caller's logits (no model, no forward pass)
+namespace {
+struct ScriptLayout {
+    size_t tokens0, tokens1, anc0, anc1, pos0, begin, sum_lp, sum_lp_next, row_done, win_done, win_done_prev, n_done, fin_tokens,
+        fin_score, fin_len, fin_count, cand_lp, cand_tok, logits, total;
+};
+ScriptLayout script_layout(int W, int G, int V, int n_ctx)
+{
+    const size_t M = (size_t)W * G, TS = (size_t)n_ctx + 1;
+    ScriptLayout L{};
+    size_t cur = 0;
+    auto take = [&](size_t bytes) { size_t o = cur; cur = align_up(cur + bytes); return o; };
+    L.tokens0 = take(M * TS * 4); L.tokens1 = take(M * TS * 4);
+    L.anc0 = take(M * n_ctx * 4); L.anc1 = take(M * n_ctx * 4);
+    L.pos0 = take(M * 4); L.begin = take((size_t)W * 4);
+    L.sum_lp = take(M * 4); L.sum_lp_next = take(M * 4); L.row_done = take(M * 4);
+    L.win_done = take((size_t)W * 4); L.win_done_prev = take((size_t)W * 4); L.n_done = take(256);
+    L.fin_tokens = take((size_t)W * FIN_CAP * TS * 4); L.fin_score = take((size_t)W * FIN_CAP * 4);
+    L.fin_len = take((size_t)W * FIN_CAP * 4); L.fin_count = take((size_t)W * 4);
+    L.cand_lp = take(M * (MAX_GROUP + 1) * 4); L.cand_tok = take(M * (MAX_GROUP + 1) * 4);
+    L.logits = take(M * (size_t)V * 4);
+    L.total = cur;
+    return L;
+}
+bool script_shape_ok(const swx_decode_cfg *cfg, int V, int n_ctx)
+{
+    return cfg && cfg->n_windows > 0 && cfg->n_group > 0 && cfg->n_group <= MAX_GROUP && V > 0 && n_ctx > 0 && cfg->sample_len > 0;
+}
+}  // namespace
+
+size_t swx_test_decode_script_ws_bytes(const swx_decode_cfg *cfg, int n_vocab, int n_ctx)
+{
+    if (!script_shape_ok(cfg, n_vocab, n_ctx)) return 0;
+    return script_layout(cfg->n_windows, cfg->n_group, n_vocab, n_ctx).total;
+}
+
+int swx_test_decode_script(const swx_decode_cfg *cfg, int n_vocab, int n_ctx, const int32_t *d_init_tokens, const int32_t *d_suppress,
+                           const uint8_t *d_ts_mask, const float *d_prefill_logits, const float *d_script, int n_script,
+                           int32_t *d_tokens_out, int32_t *d_lens_out, float *d_sumlp_out, float *d_nospeech, int32_t *d_anc_out,
+                           int32_t *d_pos0_out, void *d_ws, size_t ws_bytes, void *stream)
+{
+    if (!script_shape_ok(cfg, n_vocab, n_ctx)) return -1;
+    if (!d_init_tokens || !d_prefill_logits || !d_tokens_out || !d_lens_out || !d_sumlp_out || !d_ws) return -1;
+    if (n_script < 0 || (n_script > 0 && !d_script)) return -1;
+    const int W = cfg->n_windows, G = cfg->n_group, M = W * G, V = n_vocab;
+    if (cfg->n_suppress < 0 || cfg->n_suppress > MAX_SUPPRESS || (cfg->n_suppress > 0 && !d_suppress)) return -2;
+    for (int t : {cfg->eot, cfg->sot, cfg->timestamp_begin}) if (t < 0 || t >= V) return -2;
+    for (int t : {cfg->no_timestamps, cfg->no_speech, cfg->blank_token}) if (t < -1 || t >= V) return -2;
+    const ScriptLayout L = script_layout(W, G, V, n_ctx);
+    if (ws_bytes < L.total || ((uintptr_t)d_ws & 255)) return -8;
+    // initial tokens per window, as swx_decode reads them (sot_index plays no part: the prefill logits are the caller's)
+    int n_init = cfg->sample_begin, n_min = cfg->sample_begin;
+    if (cfg->sample_begins) {
+        n_init = *std::max_element(cfg->sample_begins, cfg->sample_begins + W);
+        n_min = *std::min_element(cfg->sample_begins, cfg->sample_begins + W);
+    }
+    if (n_min <= 0 || n_init > n_ctx) return -1;
+    const bool ragged = n_min != n_init;
+    hipStream_t s = S(stream);
+    unsigned char *ws = (unsigned char *)d_ws;
+    auto P = [&](size_t off) { return (void *)(ws + off); };
+
+    DecodeBufs b{};
+    b.cfg = *cfg;
+    b.cfg.sample_begin = n_init;
+    b.cfg.sample_begins = nullptr; b.cfg.sot_indices = nullptr; b.cfg.window_uid = nullptr;
+    if (cfg->beam || cfg->temperature == 0.f) b.cfg.noise = nullptr;
+    b.W = W; b.G = G; b.M = M; b.V = V; b.TS = n_ctx + 1; b.n_ctx = n_ctx; b.n_init = n_init;
+    const float pat = cfg->patience > 0.f ? cfg->patience : 1.0f;
+    b.max_cand = cfg->beam ? (int)lrintf((float)G * pat) : 0;
+    if (cfg->beam && (b.max_cand <= 0 || b.max_cand > FIN_CAP)) return -2;
+    b.fin_cap = FIN_CAP;
+    b.tokens[0] = (int32_t *)P(L.tokens0); b.tokens[1] = (int32_t *)P(L.tokens1);
+    const bool use_anc = G > 1;
+    b.anc[0] = use_anc ? (int32_t *)P(L.anc0) : nullptr;
+    b.anc[1] = use_anc ? (int32_t *)P(L.anc1) : nullptr;
+    b.pos0 = (int32_t *)P(L.pos0);
+    b.sum_lp = (float *)P(L.sum_lp); b.sum_lp_next = (float *)P(L.sum_lp_next);
+    b.row_done = (int32_t *)P(L.row_done);
+    b.win_done = (int32_t *)P(L.win_done); b.win_done_prev = (int32_t *)P(L.win_done_prev);
+    b.n_done = (int32_t *)P(L.n_done);
+    b.step_dev = b.n_done + 1;
+    b.fin_tokens = (int32_t *)P(L.fin_tokens); b.fin_score = (float *)P(L.fin_score);
+    b.fin_len = (int32_t *)P(L.fin_len); b.fin_count = (int32_t *)P(L.fin_count);
+    b.cand_lp = (float *)P(L.cand_lp); b.cand_tok = (int32_t *)P(L.cand_tok);
+    b.logits = (float *)P(L.logits);
+    b.suppress = d_suppress; b.ts_mask = d_ts_mask; b.win_uid = nullptr;
+    hipError_t er;
+    if (ragged) {
+        er = hipMemcpyAsync(P(L.begin), cfg->sample_begins, (size_t)W * 4, hipMemcpyHostToDevice, s);
+        if (er == hipSuccess) er = hipStreamSynchronize(s);          // the caller's array may be freed when this call returns
+        if (er != hipSuccess) return -100 - (int)er;
+        b.begin = (const int32_t *)P(L.begin);
+    }
+    er = hipMemsetAsync(b.win_done_prev, 0, (size_t)W * 4, s);
+    if (er != hipSuccess) return -100 - (int)er;
+
+    // from here on work is queued on the caller's buffers: an error return waits for it too ("blocks until the loop has finished")
+    auto fail = [&](int code) { (void)hipStreamSynchronize(s); return code; };
+    int rc = swx_decode_init(b, d_init_tokens, s);
+    if (rc >= 0) rc = swx_decode_after_prefill(b, d_prefill_logits, d_nospeech, s);
+    if (rc < 0) return fail(rc);
+    // token 0 is selected from the prefill logits, token i >= 1 from slice i - 1 of the script: eager launches, one step at a time
+    int cur = 0, steps = 0;
+    for (int i = 0; ; ++i) {
+        if (i > 0) {
+            if (i - 1 >= n_script) return fail(-2);                // the script is shorter than the loop
+            er = hipMemcpyAsync(b.logits, d_script + (size_t)(i - 1) * M * V, (size_t)M * V * 4, hipMemcpyDeviceToDevice, s);
+            if (er != hipSuccess) return fail(-100 - (int)er);
+        }
+        rc = swx_decode_select(b, cur, s);
+        if (rc < 0) return fail(rc);
+        if (cfg->beam) cur ^= 1;
+        steps = i + 1;
+        const int stop = decode_loop_stop(i, n_min, n_ctx, cfg->min_tokens, cfg->sample_len, W, b.n_done, s);
+        if (stop < 0) return fail(stop);
+        if (stop) break;
+    }
+    rc = swx_decode_finalize(b, cur, steps, d_tokens_out, d_lens_out, d_sumlp_out, swx_decode_gout(cfg), s);
+    if (rc < 0) return fail(rc);
+    if (use_anc && d_anc_out) {
+        er = hipMemcpyAsync(d_anc_out, b.anc[cur], (size_t)M * n_ctx * 4, hipMemcpyDeviceToDevice, s);
+        if (er != hipSuccess) return fail(-100 - (int)er);
+    }
+    if (d_pos0_out) {
+        er = hipMemcpyAsync(d_pos0_out, b.pos0, (size_t)M * 4, hipMemcpyDeviceToDevice, s);
+        if (er != hipSuccess) return fail(-100 - (int)er);
+    }
+    er = hipStreamSynchronize(s);
+    if (er != hipSuccess) return -100 - (int)er;
+    return steps;
 }
 
 }  // extern "C"
