@@ -18,7 +18,7 @@ still to align, ``pending`` = the last trusted word of the previous window that 
 import re
 import warnings
 from dataclasses import dataclass
-from typing import Callable, List, Optional, Sequence, Tuple, Union
+from typing import Callable, Generator, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -260,10 +260,11 @@ class Aligner:
         return [w for g in groups for w in g]
 
     def _infer(self, audio_segment: torch.Tensor, words: List[WordToken], cuts: List[int], pad_first: bool,
-               time_offset: Optional[float] = None) -> List[TimedWord]:
-        """Call the inference function for one window (:657-729)."""
+               time_offset: Optional[float] = None):
+        """One window's inference (:657-729) as a step of :meth:`steps`: yields the request ``(audio_segment, asked words)``,
+        is sent what the inference function answers, returns the window's timed words."""
         asked = self._with_gap_padding(words, cuts, pad_first)
-        got = self.inference_func(audio_segment, asked)
+        got = yield audio_segment, asked
         return self._assemble(asked, got, audio_segment.size(-1), self.time_offset if time_offset is None else time_offset)
 
     def _assemble(self, asked: List[WordToken], got: List[dict], n_samples: int, time_offset: float) -> List[TimedWord]:
@@ -476,6 +477,22 @@ class Aligner:
 
     # ------------------------------------------------------------------------------------------------- driver
     def align(self, audio: torch.Tensor, text) -> Optional[WhisperResult]:
+        """The sequential driver of :meth:`steps`: every request is answered by ``inference_func`` on the spot."""
+        steps = self.steps(audio, text)
+        try:
+            request = next(steps)
+            while True:
+                request = steps.send(self.inference_func(*request))
+        except StopIteration as done:
+            return done.value
+
+    def steps(self, audio: torch.Tensor, text) -> Generator[Tuple[torch.Tensor, List[WordToken]], List[dict], Optional[WhisperResult]]:
+        """The window state machine of one recording as a generator: yields ``(audio_segment, asked_words)`` where a window
+        needs the inference function, receives its list of word dicts, and returns what ``align`` returns.  A window depends
+        on the one before it, recordings do not depend on each other: ``align`` answers each request at once, a lockstep
+        driver (``stable_ts_amd.many.align_many``) answers the current requests of many recordings with one device pass.  A
+        recording without a window to infer (all silence) returns without yielding.  Warnings are attributed to the caller
+        of the function that drives the generator."""
         self._reset()
         self._load_text(text)
         self.audio = _MemoryAudio(audio, self.sample_rate)
@@ -494,7 +511,7 @@ class Aligner:
             segment = self._skip_nonspeech(segment)
             if segment is None:
                 continue
-            self.curr = self._infer(segment, *self._take_window_words())
+            self.curr = yield from self._infer(segment, *self._take_window_words())
             self.window = [WordToken(w.word, w.tokens) for w in self.curr]
             last_ts = self._settle_window(segment.shape[-1])
             if self.progress_callback is not None:
@@ -507,13 +524,13 @@ class Aligner:
         if self.pending is not None:
             done.append(self.pending)
         if not done:
-            warnings.warn("Failed to align text.", stacklevel=2)
+            warnings.warn("Failed to align text.", stacklevel=3)
         if self.failure_count > self.max_fail:
             warnings.warn(f"Alignment aborted. Failed word percentage exceeded {self.failure_threshold * 100}% at "
-                          f"{self.seek / self.sample_rate:.3f}s.", stacklevel=2)
+                          f"{self.seek / self.sample_rate:.3f}s.", stacklevel=3)
         elif self.queue:
             warnings.warn(f"Failed to align the last {len(self.queue)}/{self.total_words} words after "
-                          f"{(done[-1].end if done else 0):.3f}s.", stacklevel=2)
+                          f"{(done[-1].end if done else 0):.3f}s.", stacklevel=3)
         if self.queue and not self.remove_instant_words:
             eof = self.audio.get_duration(3)
             done.extend(TimedWord(w.word, eof, eof, w.tokens, 0.0) for w in self.queue)
@@ -536,7 +553,7 @@ class Aligner:
             result.regroup(self.regroup)
         n_bad = sum(1 for s in result.segments if s.end - s.start <= 0)
         if n_bad:
-            warnings.warn(f"{n_bad}/{len(result.segments)} segments failed to align.", stacklevel=2)
+            warnings.warn(f"{n_bad}/{len(result.segments)} segments failed to align.", stacklevel=3)
         return result
 
     # ------------------------------------------------------------------------------------------- align_words

@@ -31,7 +31,10 @@ def make_alignment_func(model, tokenizer, extra_models: Optional[list] = None, d
     def compute_timestamps(audio_segment: torch.Tensor, word_tokens: List[WordToken]) -> List[dict]:
         return compute_timestamps_batch([audio_segment], [word_tokens])[0]
 
-    def compute_timestamps_batch(audio_segments: Sequence[torch.Tensor], word_tokens_list: Sequence[List[WordToken]]):
+    def compute_timestamps_batch(audio_segments: Sequence[torch.Tensor], word_tokens_list: Sequence[List[WordToken]],
+                                 tokenizers: Optional[Sequence] = None):
+        """``tokenizers``: one per window where the windows belong to recordings in different languages (``align_many``);
+        every window then carries its own sot sequence and splits its words by its own language, in the same device job."""
         from . import transcribe as _tr                     # diagnostic stage timer (bench.py --phase-times), off by default
         import time
         t_ph = time.perf_counter() if _tr.PHASE_TIMES is not None else 0.0
@@ -46,8 +49,8 @@ def make_alignment_func(model, tokenizer, extra_models: Optional[list] = None, d
         for k, wts in zip(n, word_tokens_list):
             seg = dict(seek=0, tokens=([w.word for w in wts], [list(w.tokens) for w in wts]))
             windows.append(dict(segments=[seg], num_samples=k))
-        add_word_timestamps_batch(model=model, tokenizer=tokenizer, windows=windows, xkv=xkv,
-                                  split_callback=lambda x, _: x, gap_padding=None,
+        add_word_timestamps_batch(model=model, tokenizer=tokenizer if tokenizers is None else list(tokenizers),
+                                  windows=windows, xkv=xkv, split_callback=lambda x, _: x, gap_padding=None,
                                   prepend_punctuations="", append_punctuations="", extra_models=extra_models,
                                   dynamic_heads=dynamic_heads, aligner=aligner, mel=mel if extra_models else None)
         _tr._phase("align: word timestamps (scoring pass + a7 + DTW + host)", t_ph)
@@ -100,6 +103,40 @@ def make_refinement_func(model, tokenizer):
     return inference_func
 
 
+def _checked_token_step(model, token_step: int) -> int:
+    max_step = model.dims.n_text_ctx - 6                       # alignment.py:181-185
+    if token_step < 1:
+        return max_step
+    if token_step > max_step:
+        raise ValueError(f"The max value for [token_step] is {max_step} but got {token_step}.")
+    return token_step
+
+
+def _alignment_tokenizer(model, text, language, tokenizer=None):
+    """the tokenizer ``align`` works with: the caller's, or the one of ``language`` (a WhisperResult text brings its own)"""
+    if tokenizer is not None:
+        return tokenizer
+    if not language and model.is_multilingual and (language := getattr(text, "language", None)) is None:
+        raise TypeError("expected argument for language")                                  # alignment.py:375-383
+    return get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=language or "en", task="transcribe")
+
+
+def _language_code(tokenizer) -> Optional[str]:
+    return getattr(tokenizer, "language_code", None) or getattr(tokenizer, "language", None)
+
+
+def _result_language(model, tokenizer, language) -> Optional[str]:
+    return _language_code(tokenizer) or language or (None if model.is_multilingual else "en")    # alignment.py:388-393
+
+
+def _new_aligner(inference_func, tokenizer, **options):
+    """``Aligner`` over this package's audio constants with the word splitting of the tokenizer's language"""
+    from .aligner import Aligner
+    return Aligner(inference_func=inference_func, decode=tokenizer.decode, encode=tokenizer.encode,
+                   split_words_by_space=_language_code(tokenizer) not in {"zh", "ja", "th", "lo", "my"}, sample_rate=SAMPLE_RATE,
+                   max_segment_length=N_SAMPLES, **options)
+
+
 @host_single_thread
 def align(model, audio, text: Union[str, List[int], WhisperResult], language: str = None, *, tokenizer=None,
           ignore_compatibility: bool = False, remove_instant_words: bool = False, token_step: int = 100,
@@ -111,31 +148,20 @@ def align(model, audio, text: Union[str, List[int], WhisperResult], language: st
     re-alignment policy -- is :class:`stable_ts_amd.aligner.Aligner`, a restatement of the reference's ``Aligner`` that is
     checked against it window for window on CPU; each window's timestamps come from the device through
     ``make_alignment_func`` (seam B2).  Returns None when nothing could be aligned."""
-    from .aligner import Aligner
     from .transcribe import as_waveform, pop_audio_options
     audio_options = pop_audio_options(options)
-    max_step = model.dims.n_text_ctx - 6                       # alignment.py:181-185
-    if token_step < 1:
-        token_step = max_step
-    elif token_step > max_step:
-        raise ValueError(f"The max value for [token_step] is {max_step} but got {token_step}.")
-    if tokenizer is None:
-        if not language and model.is_multilingual and (language := getattr(text, "language", None)) is None:
-            raise TypeError("expected argument for language")                                  # alignment.py:375-383
-        tokenizer = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=language or "en",
-                                  task="transcribe")
-    lang_code = getattr(tokenizer, "language_code", None) or getattr(tokenizer, "language", None)
+    token_step = _checked_token_step(model, token_step)
+    tokenizer = _alignment_tokenizer(model, text, language, tokenizer)
     variant = {k: options.pop(k) for k in ("extra_models", "dynamic_heads", "aligner") if k in options}
-    aligner = Aligner(inference_func=make_alignment_func(model, tokenizer, **variant), decode=tokenizer.decode, encode=tokenizer.encode,
-                      split_words_by_space=lang_code not in {"zh", "ja", "th", "lo", "my"}, sample_rate=SAMPLE_RATE,
-                      max_segment_length=N_SAMPLES, remove_instant_words=remove_instant_words, token_step=token_step,
-                      original_split=original_split, word_dur_factor=word_dur_factor, max_word_dur=max_word_dur,
-                      nonspeech_skip=nonspeech_skip, fast_mode=fast_mode, failure_threshold=failure_threshold, **options)
+    aligner = _new_aligner(make_alignment_func(model, tokenizer, **variant), tokenizer, remove_instant_words=remove_instant_words,
+                           token_step=token_step, original_split=original_split, word_dur_factor=word_dur_factor,
+                           max_word_dur=max_word_dur, nonspeech_skip=nonspeech_skip, fast_mode=fast_mode,
+                           failure_threshold=failure_threshold, **options)
     # the waveform stays where it is: windows of a recording that is resident on the GPU are analysed there (device probe of
     # the silence analysis) and are not uploaded again
     result = aligner.align(as_waveform(audio, **audio_options).detach().float(), text)
     if result is not None:
-        result.language = lang_code or language or (None if model.is_multilingual else "en")    # alignment.py:388-393
+        result.language = _result_language(model, tokenizer, language)
     return result
 
 
