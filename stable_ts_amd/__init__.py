@@ -13,6 +13,9 @@ __version__ = "0.1.0"
 from .model import BENCH_WEIGHTS, Whisper, available_models, dims_for, load_model, random_state_dict  # noqa: F401
 from .engine import Engine, ModelDimensions  # noqa: F401
 from .result import Segment, WhisperResult, WordTiming  # noqa: F401
+from .text_output import (  # noqa: F401
+    load_result, result_to_ass, result_to_srt_vtt, result_to_tsv, result_to_txt, save_as_json,
+)
 from .decoding import DecodingOptions, DecodingResult  # noqa: F401
 from .transcribe import transcribe_stable  # noqa: F401
 from .audio_io import AudioLoader, load_audio, prep_audio  # noqa: F401

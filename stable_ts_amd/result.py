@@ -14,6 +14,7 @@ import warnings
 from typing import Iterator, List, Optional, Union
 
 from ._num import round3
+from .text_output import result_to_ass, result_to_srt_vtt, result_to_tsv, result_to_txt
 
 
 def _ms(ts):
@@ -497,16 +498,58 @@ class Segment:
             self._default_start, self._default_end = self.start, self.end
             self.words = None
 
-    def to_dict(self) -> dict:
-        toks = self.tokens
-        d = dict(start=self.start, end=self.end, text=self.text, seek=self.seek,
-                 tokens=None if toks is None else list(toks), temperature=self.temperature,
-                 avg_logprob=self.avg_logprob, compression_ratio=self.compression_ratio,
-                 no_speech_prob=self.no_speech_prob)
-        if self.words:
-            d["words"] = [w.to_dict() for w in self.words]
-        elif self.words is not None:
+    def _with_punctuation_swapped(self, prepend_punctuations: Optional[str] = None,
+                                  append_punctuations: Optional[str] = None) -> "Segment":
+        """result.py:562-607, the segment that ``to_dict(reverse_text=...)`` writes: a copy in which every word's
+        leading prepend-punctuation (the space included) has moved behind the word and its trailing
+        append-punctuation in front of it.  The order of the words stays; only a segment without words gets its text
+        rebuilt from its space-separated pieces in reverse order."""
+        warnings.warn("``_to_reverse_text()`` is deprecated and will be removed in future versions.",
+                      category=DeprecationWarning, stacklevel=2)
+        from .timing import APPEND_PUNCTUATIONS, PREPEND_PUNCTUATIONS
+        lead = PREPEND_PUNCTUATIONS if prepend_punctuations is None else prepend_punctuations
+        if lead and " " not in lead:
+            lead += " "
+        trail = APPEND_PUNCTUATIONS if append_punctuations is None else append_punctuations
+        seg = self.copy(copy_words=True)
+        if not (lead or trail):
+            return seg
+        pieces = seg.words if seg.words else [WordTiming(t, 0, 1, 0) for t in seg.text.split(" ")]
+        for w in pieces:
+            core = w.word
+            n_lead = 0
+            if lead:
+                while n_lead < len(core) and core[n_lead] in lead:
+                    n_lead += 1
+            moved_back, core = core[:n_lead], core[n_lead:]
+            n_trail = 0
+            if trail:
+                while n_trail < len(core) and core[-1 - n_trail] in trail:
+                    n_trail += 1
+            moved_front, core = core[len(core) - n_trail:], core[:len(core) - n_trail]
+            w.word = moved_front[::-1] + core + moved_back[::-1]
+        seg._default_text = "".join(w.word for w in reversed(pieces))
+        return seg
+
+    def to_dict(self, reverse_text: Union[bool, tuple] = False) -> dict:
+        seg = self
+        if reverse_text:
+            warnings.warn("``reverse_text=True`` is deprecated and will be removed in future versions. "
+                          "RTL text playback issues are caused by the video player incorrectly parsing tags "
+                          "(note: tags come from ``segment_level=True + word_level=True``).")
+            # the value is the (prepend_punctuations, append_punctuations) pair; a bare True is a TypeError upstream too
+            seg = self._with_punctuation_swapped(*reverse_text)
+        toks = seg.tokens
+        d = dict(start=seg.start, end=seg.end, text=seg.text, seek=seg.seek,
+                 tokens=None if toks is None else list(toks), temperature=seg.temperature,
+                 avg_logprob=seg.avg_logprob, compression_ratio=seg.compression_ratio,
+                 no_speech_prob=seg.no_speech_prob)
+        if seg.words:
+            d["words"] = [w.to_dict() for w in seg.words]
+        elif seg.words is not None:
             d["words"] = []
+        if reverse_text:
+            d["reversed_text"] = True
         return d
 
 
@@ -776,8 +819,8 @@ class WhisperResult:
             return [sg.words_by_lock(only_text=only_text, include_single=include_single) for sg in self.segments]
         return group_by_lock(self.all_words(), only_text=only_text, include_single=include_single)
 
-    def segments_to_dicts(self) -> List[dict]:
-        return [sg.to_dict() for sg in self.segments]
+    def segments_to_dicts(self, reverse_text: Union[bool, tuple] = False) -> List[dict]:
+        return [sg.to_dict(reverse_text=reverse_text) for sg in self.segments]
 
     def find(self, pattern: str, word_level: bool = True, flags=None) -> "WhisperResultMatches":
         """Regular-expression search over the text; the matches carry the segments / words they span (result.py:3026)."""
@@ -930,6 +973,8 @@ class WhisperResult:
                     nonspeech_sections=self._nonspeech_sections, unfinished=self.unfinished_start)
 
     def save_as_json(self, path: str):
+        """The result without ``ori_dict``, written to ``path`` as given.  The stable-ts shaped function (``.json``
+        appended, ``ori_dict`` kept, ``Saved:`` printed) is :func:`stable_ts_amd.text_output.save_as_json`."""
         d = self.to_dict(keep_orig=False)
         d.pop("ori_dict", None)
         with open(path, "w", encoding="utf-8") as f:
@@ -1142,6 +1187,12 @@ class WhisperResult:
     def parse_regroup_algo(self, regroup_algo: str, include_str: bool = True):
         from . import regroup as R
         return R.parse_regroup_algo(self, regroup_algo, include_str)
+
+    # -- writers (text_output.py), bound as the reference binds them (result.py:3098-3101)
+    to_srt_vtt = result_to_srt_vtt
+    to_ass = result_to_ass
+    to_tsv = result_to_tsv
+    to_txt = result_to_txt
 
 
 class SegmentMatch:
