@@ -271,6 +271,17 @@ int swx_loudness_probe(const float *d_pcm, int64_t pcm_stride, const int32_t *d_
  * the chip (a forced-alignment pass analyses one window per call); without it one workgroup per window.  The same element either way. */
 size_t swx_loudness_probe_scratch_bytes(int W);
 
+/* ---- probe audio that stays on the device (refine_many): the edits of one bisection round applied to the probe rows in one launch.
+ * d_probe f32 [n_rows] rows `stride` samples apart; probe row r belongs to clean row r >> 1 of d_clean f32 [(n_rows + 1) / 2] rows of
+ * the same stride.  d_ops int32 [n_ops][4] = {row, a, b, kind} in DEVICE memory, stably sorted by row; d_row_start int32
+ * [n_rows + 1] (device) = the offset of every row's ops in that list.  kind 0 writes +0.0f to [a, b) of the row, kind 1 copies
+ * [a, b) from the row's clean row.  The ops are ordered writes: for every sample the LAST op of its row that covers it decides
+ * its bits, a sample that no op covers keeps its bits.  An op whose row is not the row it is listed under (any row outside
+ * [0, n_rows) is such an op) or whose kind is unknown is ignored; a, b are clamped to [0, stride]; nothing outside the two buffers
+ * is dereferenced.  n_ops == 0 launches nothing.  The call only enqueues on `stream`: no synchronisation, no allocation. */
+int swx_pcm_edit(const float *d_clean, float *d_probe, int64_t stride, int n_rows, const int32_t *d_ops,
+                 const int32_t *d_row_start, int n_ops, void *stream);
+
 /* ---- f2 audio front-end: FLAC decoding on the HOST (no device work; csrc/swx_flac.hip).  The reference pipes every container
  * through an `ffmpeg -f s16le` child process (stable_whisper/audio/utils.py:63-125); offline boxes have no ffmpeg and the
  * reference's only real-speech fixture is test/jfk.flac, so native FLAC streams are decoded here: STREAMINFO + frames with

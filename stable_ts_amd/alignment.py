@@ -80,24 +80,42 @@ def make_refinement_func(model, tokenizer):
         logits = model.engine.forward_logits(xkv, [ids, ids])
         return logits[:, len(sot): len(sot) + len(tokens), : tokenizer.eot].softmax(dim=-1)
 
-    def inference_batch(items: Sequence[Tuple[torch.Tensor, List[int]]]) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    def inference_batch(items: Sequence[Tuple[torch.Tensor, List[int]]], tokenizers: Optional[Sequence] = None,
+                        resident: Optional[Tuple[torch.Tensor, Sequence[int]]] = None) -> List[Tuple[torch.Tensor, torch.Tensor]]:
         """[(audio[2, n_g], tokens_g)] -> [(p[2, T_g], rank[2, T_g])] (host tensors): ONE mel / encoder / cross-KV / decoder
         pass over all 2 G windows, ragged in audio length and token count.  Each pair of copies keeps its own log-mel clamp
         floor (``swx_log_mel_ragged_grouped``), and of every row of the pass only the target token's probability and its rank
-        in the row leave the device (``swx_forward_token_ranks``) -- the two numbers per token the bisection reads."""
+        in the row leave the device (``swx_forward_token_ranks``) -- the two numbers per token the bisection reads.
+        ``tokenizers``: one per item where the groups belong to recordings in different languages (``refine_many``); every pair
+        of windows then carries its own sot sequence.  ``resident = (pcm f32 [2 G, 480000] on the device, n_valid [2 G])``: the
+        probes already lie there in the items' order (``refine_many``'s probe rows, read in place); the items' audio is not looked
+        at and nothing is staged or uploaded."""
         if not items:
             return []
-        segs, ids = [], []
-        for audio_segment, tokens in items:
-            audio_segment = audio_segment[..., :N_SAMPLES]
-            segs += [audio_segment[0], audio_segment[1]]
-            ids += [[*sot, tokenizer.no_timestamps, *[int(t) for t in tokens], tokenizer.eot]] * 2
-        mel = model.log_mel_segments(segs, group=2)
+        toks = [tokenizer] * len(items) if tokenizers is None else list(tokenizers)
+        if len(toks) != len(items):
+            raise ValueError(f"{len(toks)} tokenizers for {len(items)} items")
+        segs, ids, lead = [], [], []
+        for (audio_segment, tokens), tok in zip(items, toks):
+            if resident is None:
+                audio_segment = audio_segment[..., :N_SAMPLES]
+                segs += [audio_segment[0], audio_segment[1]]
+            head = list(tok.sot_sequence)
+            lead.append(len(head))
+            ids += [[*head, tok.no_timestamps, *[int(t) for t in tokens], tok.eot]] * 2
+        if resident is None:
+            mel = model.log_mel_segments(segs, group=2)
+        else:
+            pcm, n_valid = resident
+            if pcm.shape[0] != 2 * len(items) or len(n_valid) != 2 * len(items):
+                raise ValueError(f"{pcm.shape[0]} resident rows and {len(n_valid)} lengths for {len(items)} items")
+            n_valid = [int(n) for n in n_valid]
+            mel = model.engine.log_mel_ragged(pcm, n_valid, n_valid, per_item_max=False, group=2)
         xkv = model.cross_kv(model.encoder(mel))
         prob, rank = model.engine.forward_token_ranks(xkv, ids, n_vocab_used=tokenizer.eot)
         prob, rank = prob.cpu(), rank.cpu()
-        return [(prob[2 * g: 2 * g + 2, len(sot): len(sot) + len(tokens)], rank[2 * g: 2 * g + 2, len(sot): len(sot) + len(tokens)])
-                for g, (_, tokens) in enumerate(items)]
+        return [(prob[2 * g: 2 * g + 2, k: k + len(tokens)], rank[2 * g: 2 * g + 2, k: k + len(tokens)])
+                for g, ((_, tokens), k) in enumerate(zip(items, lead))]
 
     inference_func.batch = inference_batch
     return inference_func

@@ -566,6 +566,52 @@ def loudness_probe(chunks: Sequence[torch.Tensor]) -> list:
     return res
 
 
+PCM_EDIT_SPAN = 4096        # samples one workgroup of swx_pcm_edit owns (csrc/swx_pcm.hip PE_SPAN)
+PCM_EDIT_BATCH = 128        # ops it stages in LDS at a time (PE_BATCH)
+
+
+def pcm_edit_plan(ops, n_rows: int) -> Tuple[np.ndarray, np.ndarray]:
+    """``(ops [n, 4] int32 stably sorted by row, row_start [n_rows + 1] int32)``: the two lists ``swx_pcm_edit`` reads.  An op
+    whose row lies outside ``[0, n_rows)`` ends up outside every row's range."""
+    ops = np.asarray(ops, dtype=np.int64).reshape(-1, 4)
+    ops = ops[np.argsort(ops[:, 0], kind="stable")]
+    row_start = np.searchsorted(ops[:, 0], np.arange(n_rows + 1), side="left").astype(np.int32)
+    return np.ascontiguousarray(ops.astype(np.int32)), row_start
+
+
+def pcm_edit(clean: torch.Tensor, probe: torch.Tensor, ops, n_rows: Optional[int] = None, validate: bool = True) -> int:
+    """The edits of one bisection round applied to probe audio that lives on the device (``swx_pcm_edit``, one launch).
+    ``probe`` f32 [R, stride] and ``clean`` f32 [>= (R + 1) // 2, stride] on one device; ``ops`` = ``(row, a, b, kind)`` in issue
+    order, kind 0 writes +0.0 to ``probe[row, a:b]``, kind 1 copies ``clean[row >> 1, a:b]`` there.  They are ordered writes: for
+    every sample the last op of its row that covers it decides.  Only enqueues (the op list is one small upload); returns the
+    number of ops sent.  ``validate``: refuse an op with a row outside ``[0, n_rows)``, an unknown kind or bounds outside
+    ``0 <= a <= b <= stride`` instead of leaving it to the kernel to ignore or clamp it."""
+    lib = _lib.load()
+    assert clean.is_cuda and probe.is_cuda and clean.device == probe.device
+    assert clean.dtype == torch.float32 and probe.dtype == torch.float32 and clean.ndim == 2 and probe.ndim == 2
+    assert clean.is_contiguous() and probe.is_contiguous() and clean.shape[1] == probe.shape[1]
+    stride = int(probe.shape[1])
+    n_rows = int(probe.shape[0]) if n_rows is None else int(n_rows)
+    if not 0 < n_rows <= probe.shape[0] or (n_rows + 1) // 2 > clean.shape[0]:
+        raise ValueError(f"n_rows = {n_rows} for {probe.shape[0]} probe rows and {clean.shape[0]} clean rows")
+    arr = np.asarray(ops, dtype=np.int64).reshape(-1, 4)
+    if len(arr) == 0:
+        return 0
+    if validate:
+        bad = (arr[:, 0] < 0) | (arr[:, 0] >= n_rows) | (arr[:, 3] < 0) | (arr[:, 3] > 1) | (arr[:, 1] < 0) | \
+            (arr[:, 1] > arr[:, 2]) | (arr[:, 2] > stride)
+        if bad.any():
+            raise ValueError(f"bad pcm edit {tuple(arr[int(np.argmax(bad))])} for {n_rows} rows of {stride} samples")
+    elif np.abs(arr).max() > 0x7FFFFFFF:
+        raise ValueError("pcm edit does not fit int32")
+    sorted_ops, row_start = pcm_edit_plan(arr, n_rows)
+    d_lists = torch.from_numpy(np.concatenate([sorted_ops.reshape(-1), row_start])).to(probe.device)   # one upload for both lists
+    stream = ctypes.c_void_p(torch.cuda.current_stream(probe.device).cuda_stream)
+    check(lib.swx_pcm_edit(_ptr(clean), _ptr(probe), stride, n_rows, _ptr(d_lists), _ptr(d_lists[4 * len(sorted_ops):]),
+                           len(sorted_ops), stream), "swx_pcm_edit")
+    return len(sorted_ops)
+
+
 def median_filter(x: torch.Tensor, width: int) -> torch.Tensor:
     """whisper.timing.median_filter on the device (f32, last axis)."""
     lib = _lib.load()

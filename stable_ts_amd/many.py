@@ -22,8 +22,18 @@ depends on the DTW result of the window before it.  Between recordings nothing d
 machine of every recording (``Aligner.steps``, the generator ``Aligner.align`` itself drives) is advanced to its next
 inference request and the requests of a round -- ragged in audio length, token count and language -- are answered by one
 ``make_alignment_func(...).batch`` call: one mel / encoder / cross-K/V / scoring / DTW job for up to ``max_tracks`` windows.
+
+``refine_many`` does it for ``refine``.  ``refine(batch_size=N)`` bisects the word groups of ONE recording in lockstep, and a clip
+of a few seconds is one or two groups, so its rounds hold 2-4 windows whatever N is.  Here the groups of all recordings share
+the rounds (``stable_ts_amd.refiner.refine_tracks``: every group is the generator ``refine`` runs, a recording's steps stay in
+order), answered by one ``make_refinement_func(...).batch`` call of 2 x (groups in flight) windows.  With ``device_probes=True`` the
+two audio copies of every group live on the device (``DeviceProbes``): the clean segment is uploaded once when the group takes
+a slot, and a round sends only the bisection's edits -- at most one interval per unfinished word -- as an ordered op list that
+one launch of ``swx_pcm_edit`` applies; the log-mel reads the probe rows in place.
 """
 from typing import Any, List, Optional, Sequence, Union
+
+import torch
 
 from .result import WhisperResult
 from .stabilization import host_single_thread
@@ -184,3 +194,129 @@ def align_many(model, audios: Sequence, texts: Sequence[Union[str, List[int], Wh
         for _, steps, _ in live:
             steps.close()
     return results
+
+
+class DeviceProbes:
+    """The probe audio of the groups in flight, resident on the device: ``clean`` f32 [max_tracks][480000] (a group's clean
+    segment, uploaded once when it takes a slot) and ``probe`` f32 [2 * max_tracks][480000] (probe row r belongs to clean row
+    r >> 1).  A round's list position is the slot; ``refine_tracks`` keeps the live slots dense, so rows ``[0, 2 * live)`` are what
+    the log-mel reads, in place.  ``sync(probes)`` brings the device up to date with the round's ``OpsProbe`` objects: a probe
+    that is new takes its slot (upload + a restore over ``[0, n)`` of both rows), one that sits in another slot is moved (a
+    device-to-device copy; only the highest live slot ever moves, into a hole at the tail of a run), and the edits every probe
+    recorded since the last round go out as ONE op list and ONE launch, rows offset by the slot."""
+
+    def __init__(self, max_tracks: int, device):
+        from .audio import N_SAMPLES
+        self.n_samples = N_SAMPLES
+        # uninitialised: a slot is filled over [0, n) when a group takes it and the log-mel never reads past a row's n_valid
+        self.clean = torch.empty(max_tracks, N_SAMPLES, dtype=torch.float32, device=device)
+        self.probe = torch.empty(2 * max_tracks, N_SAMPLES, dtype=torch.float32, device=device)
+        self.slots: list = [None] * max_tracks
+
+    def sync(self, probes: Sequence) -> tuple:
+        """-> ``(probe rows [2 * len(probes), 480000] (a view), n_valid per row)``"""
+        from .engine import pcm_edit
+        if len(probes) > len(self.slots):
+            raise ValueError(f"{len(probes)} probes for {len(self.slots)} slots")
+        ops: list = []
+        where = {id(p): k for k, p in enumerate(self.slots) if p is not None}
+        for k, p in enumerate(probes):
+            if self.slots[k] is p:
+                continue
+            j = where.get(id(p))
+            if j is None:                                           # a new group: its clean segment goes up once
+                self.clean[k, :p.n_kept] = p.clean[0, :p.n_kept].to(self.clean.device)
+                ops += [(2 * k, 0, p.n_kept, 1), (2 * k + 1, 0, p.n_kept, 1)]
+            else:                                                   # the highest live slot moves into a hole
+                self.clean[k].copy_(self.clean[j])
+                self.probe[2 * k: 2 * k + 2].copy_(self.probe[2 * j: 2 * j + 2])
+        self.slots = list(probes) + [None] * (len(self.slots) - len(probes))
+        for k, p in enumerate(probes):
+            ops += [(2 * k + row, a, b, kind) for row, a, b, kind in p.take()]
+        if ops:
+            pcm_edit(self.clean, self.probe, ops, n_rows=2 * len(probes))
+        return self.probe[: 2 * len(probes)], [p.n_kept for p in probes for _ in range(2)]
+
+
+@host_single_thread
+def refine_many(model, audios: Sequence, results: Sequence[WhisperResult], *, max_tracks: int = 16, device_probes: bool = False,
+                **refine_options) -> List[WhisperResult]:
+    """``[model.refine(a, r, **refine_options) for a, r in zip(audios, results)]`` with the word groups of all recordings bisected
+    in lockstep: up to ``max_tracks`` groups of any recordings per device pass (2 windows each), every result equal to the one of
+    ``refine`` alone, in input order.  ``audios``: whatever ``refine`` takes per item.  ``results``: a ``WhisperResult`` per
+    recording; one without words or probabilities goes through ``align_words`` first, as in ``refine`` (a result without any
+    words comes back as it is; ``refine`` alone raises IndexError there).  Options are those of ``refine`` except ``batch_size``;
+    ``inplace`` applies per result; ``progress_callback(seconds_done, seconds_total)`` counts all recordings.
+    ``device_probes=True``: the probe audio stays on the device and a round uploads only the bisection's edits (``swx_pcm_edit``)
+    instead of rebuilding the probes on the host and uploading them every round; the same PCM bits reach the model either way.
+    Off by default: measured, it is not faster beyond the spread of the repeats.  The device workspace
+    grows to ``2 * max_tracks`` windows and no further (with device probes plus 3 x 1.92 MB x ``max_tracks`` of probe audio)."""
+    from . import alignment as A
+    from .audio import N_SAMPLES, SAMPLE_RATE
+    from .refiner import OpsProbe, Refiner, refine_tracks
+    from .tokenizer import get_tokenizer
+    from .transcribe import _with_index, as_waveform, pop_audio_options
+    if refine_options.get("batch_size") is not None:
+        raise NotImplementedError("batch_size does not combine with refine_many")
+    if isinstance(audios, (str, bytes)) or not hasattr(audios, "__len__") or hasattr(audios, "shape"):
+        raise TypeError("audios must be a list of recordings (refine() takes a single one)")
+    audios = list(audios)
+    if isinstance(results, WhisperResult) or not hasattr(results, "__len__"):
+        raise TypeError("results must be a list with one WhisperResult per recording")
+    results = list(results)
+    if len(results) != len(audios):
+        raise ValueError(f"results has {len(results)} entries for {len(audios)} recordings")
+    if max_tracks is None or isinstance(max_tracks, bool) or int(max_tracks) != max_tracks or int(max_tracks) < 1:
+        raise ValueError(f"max_tracks must be an integer of at least 1, got {max_tracks}")
+    max_tracks = int(max_tracks)
+    options = dict(refine_options)
+    audio_options = pop_audio_options(options)
+    for k in ("batch_size", "single_batch"):                       # named arguments of refine() without effect here
+        options.pop(k, None)
+    inplace = options.pop("inplace", True)
+    progress_callback = options.pop("progress_callback", None)
+    if not audios:
+        return []
+
+    # ---- everything that can be refused is refused here, before any recording is decoded or any device work is queued
+    by_language: dict = {}
+    refiners, to_align = [], []
+    for i, result in enumerate(results):
+        if not isinstance(result, WhisperResult):
+            raise TypeError(f"results[{i}] is not a WhisperResult")
+        needs_words = bool(result) and (not result.has_words or any(w.probability is None for w in result.all_words()))
+        if needs_words and not result.language:
+            raise _with_index(RuntimeError("cannot align words with result missing language"), i)
+        to_align.append(needs_words)
+        key = result.language or "en"
+        if key not in by_language:
+            by_language[key] = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=key,
+                                             task="transcribe")
+        refiners.append(Refiner(None, sample_rate=SAMPLE_RATE, max_inference_tokens=model.dims.n_text_ctx - 6, **options))
+    tokenizers = [by_language[r.language or "en"] for r in results]
+    func = A.make_refinement_func(model, tokenizers[0])
+
+    work: List[WhisperResult] = []
+    for i, (audio, result) in enumerate(zip(audios, results)):
+        try:
+            if to_align[i]:
+                result = A.align_words(model, audio, result)
+            wave = as_waveform(audio, **audio_options)
+        except Exception as e:                                     # what refine() raises for this recording, with its place
+            raise _with_index(e, i) from e
+        if device_probes:
+            refiners[i].probe_buffer = lambda clean: OpsProbe(clean, limit=N_SAMPLES)
+        work.append(refiners[i]._prepare(wave, result, inplace, tokenizers[i].encode))
+
+    resident = DeviceProbes(max_tracks, model.device) if device_probes else None
+
+    def answer(flying: list) -> List[Any]:
+        """one device pass for the round's probes; ``tokenizers=`` only where the round really mixes languages"""
+        toks = [tokenizers[i] for i, _ in flying]
+        kw = {} if all(t is toks[0] for t in toks) and toks[0] is tokenizers[0] else dict(tokenizers=toks)
+        if resident is None:
+            return func.batch([(request[0], request[1]) for _, request in flying], **kw)
+        rows = resident.sync([request[0] for _, request in flying])
+        return func.batch([(None, request[1]) for _, request in flying], resident=rows, **kw)
+
+    return refine_tracks(refiners, work, max_tracks, answer, progress_callback)

@@ -23,7 +23,11 @@ words), so two drivers run the SAME generator: the sequential one (``batch_size=
 and the lockstep one (``batch_size=N``), which keeps up to N unfinished groups in flight and hands all their probes of a
 round to ``inference_func.batch`` in one call (``stable_ts_amd.alignment.make_refinement_func``: one mel / encoder /
 decoder pass over 2 N windows, answered by ``swx_forward_token_ranks`` with a probability and a rank per token instead of a
-distribution).  A group leaves the batch when all its words are done and a waiting group takes its place.
+distribution).  A group leaves the batch when all its words are done and a waiting group takes its place.  A third driver,
+``refine_tracks`` (``refine_many``), pools the groups of many recordings, each with its own ``Refiner``, in the same way.
+
+The generator writes its two audio copies through a probe buffer with two methods, mute and restore: ``HostProbe`` is the
+tensor every path above probes with, ``OpsProbe`` records the writes for copies that live on the device.
 """
 import copy
 from typing import Callable, Iterator, List, Optional, Tuple
@@ -44,7 +48,63 @@ def token_rank(row, target: int) -> int:
     return int(np.count_nonzero(row < x) + np.count_nonzero(row[:target] == x))
 
 
+class HostProbe:
+    """The two audio copies of one word group as a host tensor ``audio[2, n]``: what every probe of ``refine()`` is made of.
+    ``mute`` / ``restore`` are the only two writes the bisection makes; bounds follow the tensor's slice rules."""
+
+    def __init__(self, clean: torch.Tensor):
+        self.clean = clean
+        self.audio = clean.clone().repeat_interleave(2, 0)               # copy 0: even words, copy 1: odd words
+
+    def mute(self, row: int, a: int, b: int):
+        self.audio[row, a:b] = 0
+
+    def restore(self, row: int, a: int, b: int):
+        self.audio[row, a:b] = self.clean[0, a:b]
+
+
+class OpsProbe:
+    """The same two copies kept somewhere else (on the device, ``refine_many``): the writes are recorded as ``(row, a, b, kind)``
+    in issue order, kind 0 = mute, 1 = restore, and ``take()`` hands over what was recorded since the last call.  They are
+    ORDERED writes, not a set of muted intervals: the bisection looks a word's copy up in the per-token row table with the word
+    index, so two words can write to one row and a restore can overwrite another word's mute -- for every sample the last op of
+    its row that covers it decides.  ``a, b`` are normalised as the tensor would (``slice(a, b).indices(n)``) and clipped to the
+    ``limit`` samples a probe keeps on its way to the model; empty writes are dropped."""
+    MUTE, RESTORE = 0, 1
+
+    def __init__(self, clean: torch.Tensor, limit: Optional[int] = None):
+        self.clean = clean
+        self.n = int(clean.shape[-1])
+        self.n_kept = self.n if limit is None else min(self.n, int(limit))
+        self.ops: List[Tuple[int, int, int, int]] = []
+
+    @property
+    def audio(self):
+        return self
+
+    def _write(self, row: int, a, b, kind: int):
+        row = int(row)
+        if not 0 <= row < 2:
+            raise IndexError(f"a probe has two copies, got row {row}")
+        a, b, _ = slice(None if a is None else int(a), None if b is None else int(b)).indices(self.n)
+        b = min(b, self.n_kept)
+        if a < b:
+            self.ops.append((row, a, b, kind))
+
+    def mute(self, row: int, a, b):
+        self._write(row, a, b, self.MUTE)
+
+    def restore(self, row: int, a, b):
+        self._write(row, a, b, self.RESTORE)
+
+    def take(self) -> List[Tuple[int, int, int, int]]:
+        ops, self.ops = self.ops, []
+        return ops
+
+
 class Refiner:
+    probe_buffer = HostProbe                    # what ``_group_rounds`` keeps a group's two audio copies in
+
     def __init__(self, inference_func: Callable, sample_rate: int = 16000, max_segment_length="30s",
                  max_inference_tokens: int = 100, *, steps: str = "se", rel_prob_decrease: float = .03,
                  abs_prob_decrease: float = .05, rel_rel_prob_decrease: Optional[float] = None,
@@ -87,6 +147,18 @@ class Refiner:
     # ----------------------------------------------------------------------------------------------- driver
     def refine(self, audio: torch.Tensor, result: WhisperResult, inplace: bool = True,
                encode: Optional[Callable] = None) -> WhisperResult:
+        result = self._prepare(audio, result, inplace, encode)
+        for n, step in enumerate(self.steps, 1):
+            self._refine(result, step)
+            if self.progress_callback is not None:
+                total = round(self._audio.size(-1) / self.sample_rate, 2)
+                self.progress_callback(round(total * n / len(self.steps), 2), total)
+        result.reassign_ids()
+        return result
+
+    def _prepare(self, audio: torch.Tensor, result: WhisperResult, inplace: bool = True,
+                 encode: Optional[Callable] = None) -> WhisperResult:
+        """the result ``refine`` works on (tokens filled in, copied unless ``inplace``), with this recording's audio taken"""
         if result:
             if not result.has_words:
                 raise RuntimeError("cannot refine result with missing word-timestamps")
@@ -98,12 +170,6 @@ class Refiner:
         if not inplace:
             result = copy.deepcopy(result)
         self._audio = torch.as_tensor(audio, dtype=torch.float32).detach().cpu()
-        for n, step in enumerate(self.steps, 1):
-            self._refine(result, step)
-            if self.progress_callback is not None:
-                total = round(self._audio.size(-1) / self.sample_rate, 2)
-                self.progress_callback(round(total * n / len(self.steps), 2), total)
-        result.reassign_ids()
         return result
 
     # ------------------------------------------------------------------------------------------- grouping
@@ -265,7 +331,8 @@ class Refiner:
         mid_end = min_end + ((max_end - min_end) / 2).round().astype(np.int32)
         text_tokens = [t for w in words for t in w.tokens]
         word_tokens = [list(w.tokens) for w in words]
-        probe = clean.clone().repeat_interleave(2, 0)               # copy 0: even words, copy 1: odd words
+        buf = self.probe_buffer(clean)                              # copy 0: even words, copy 1: odd words
+        n = clean.size(-1)
         done = np.less([w.probability for w in words], self.prob_threshold)
         done = np.logical_or(done, [w.duration == 0 for w in words])
         if not self.word_level:
@@ -277,21 +344,21 @@ class Refiner:
             if done[idx]:
                 continue
             if at_end:                                               # mute from the word's end to the next word
-                stop = probe.size(-1) if idx == len(words) - 1 else mid_end[idx + 1]
-                probe[row, cut:stop] = 0
+                stop = n if idx == len(words) - 1 else mid_end[idx + 1]
+                buf.mute(row, cut, stop)
             else:                                                    # mute from the previous word up to the start
                 stop = 0 if idx == 0 else mid_start[idx - 1]
-                probe[row, stop:cut] = 0
-        ref_p, ref_rank = yield probe, text_tokens, word_tokens, rows
+                buf.mute(row, stop, cut)
+        ref_p, ref_rank = yield buf.audio, text_tokens, word_tokens, rows
         track = np.zeros((ref_p.shape[-1], 3), dtype=np.int32)       # [failed once, passed once, last good boundary]
         track[:, -1] = -1
         first_cut = (mid_end, max_start) if at_end else (min_end, mid_start)
         for idx, (s, e) in enumerate(zip(*first_cut)):
             if not done[idx]:
-                probe[idx % 2, s:e] = 0
+                buf.mute(idx % 2, s, e)
         prev_p = ref_p
         while not np.all(done):
-            p, rank = yield probe, text_tokens, word_tokens, rows
+            p, rank = yield buf.audio, text_tokens, word_tokens, rows
             abs_drop = ref_p - p
             rel_drop = abs_drop / ref_p
             step_drop = (prev_p - p) / prev_p
@@ -328,13 +395,13 @@ class Refiner:
                 new_mid = lo + half
                 if failed:                                           # give audio back
                     if at_end:
-                        probe[row, lo:new_mid] = clean[0, lo:new_mid]
+                        buf.restore(row, lo, new_mid)
                     else:
-                        probe[row, new_mid:hi] = clean[0, new_mid:hi]
+                        buf.restore(row, new_mid, hi)
                 elif at_end:                                         # mute more
-                    probe[row, new_mid:hi] = 0
+                    buf.mute(row, new_mid, hi)
                 else:
-                    probe[row, lo:new_mid] = 0
+                    buf.mute(row, lo, new_mid)
                 if at_end:
                     min_end[idx], max_end[idx], mid_end[idx] = lo, hi, new_mid
                 else:
@@ -342,3 +409,105 @@ class Refiner:
                 if not lost_rank:
                     track[idx][-1] = new_mid
                 ref_p[idx] = p[idx]
+
+
+def refine_tracks(refiners: List[Refiner], results: List[WhisperResult], max_tracks: int, answer: Optional[Callable] = None,
+                  progress_callback: Optional[Callable] = None) -> List[WhisperResult]:
+    """The word groups of many recordings bisected in lockstep (``refine_many``).  ``refiners[i]`` has taken its recording
+    (``Refiner._prepare``) and ``results[i]`` is what that call returned.  A recording runs its steps in order; within a step its
+    groups are independent and across recordings everything is, so up to ``max_tracks`` groups of any recordings are in flight,
+    every one the ``_group_rounds`` generator ``Refiner.refine`` runs, and a round's requests are answered by ONE call of
+    ``answer(flying)`` -- ``flying[k] = (recording index, request)``, one output per entry.  The place in that list is the
+    group's slot: a group that finishes hands its slot to a waiting group in the same round (a recording's next step starts
+    waiting the moment the last group of its current step finishes); when nothing waits the LAST slot moves into the hole, so the
+    live slots stay dense and only the tail of a run ever moves.  Without ``answer`` every recording's own inference function
+    answers its requests (``Refiner._infer_batch``).
+
+    A result without words comes back as it is (``Refiner.refine`` alone raises IndexError there).
+    ``progress_callback(seconds_done, seconds_total)`` counts every recording, a step at a time."""
+    max_tracks = int(max_tracks)
+    if max_tracks < 1:
+        raise ValueError(f"max_tracks must be at least 1, got {max_tracks}")
+    if len(refiners) != len(results):
+        raise ValueError(f"{len(refiners)} refiners for {len(results)} results")
+    if answer is None:
+        def answer(flying):
+            outs: list = [None] * len(flying)
+            for i in sorted({i for i, _ in flying}):
+                mine = [k for k, (j, _) in enumerate(flying) if j == i]
+                for k, out in zip(mine, refiners[i]._infer_batch([flying[k][1] for k in mine])):
+                    outs[k] = out
+            return outs
+
+    seconds = [r._audio.size(-1) / r.sample_rate for r in refiners]
+    steps_done = [0] * len(refiners)
+    open_groups = [0] * len(refiners)
+    waiting: list = []                                               # (recording, group, at_end), handed out from the front
+
+    def report():
+        if progress_callback is not None:
+            total = round(sum(seconds), 2)
+            done = sum(s * n / len(r.steps) for s, n, r in zip(seconds, steps_done, refiners))
+            progress_callback(min(round(done, 2), total), total)
+
+    def next_step(i: int):
+        """queue the groups of recording i's next step that has any; past the last step the recording is finished"""
+        r = refiners[i]
+        while steps_done[i] < len(r.steps):
+            at_end = r.steps[steps_done[i]] == "e"
+            groups = list(r._groups(results[i], round(r._audio.shape[-1] / r.sample_rate, 3))) if results[i].all_words() else []
+            if groups:
+                open_groups[i] = len(groups)
+                waiting.extend((i, g, at_end) for g in groups)
+                return
+            steps_done[i] += 1
+        results[i].reassign_ids()
+
+    def take():
+        """the next waiting group as a slot entry ``[recording, generator, at_end, request]``"""
+        i, group, at_end = waiting.pop(0)
+        rounds = refiners[i]._group_rounds(*group, at_end)
+        return [i, rounds, at_end, next(rounds)]
+
+    for i in range(len(refiners)):
+        next_step(i)
+    flying: list = []
+    try:
+        while waiting or flying:
+            while waiting and len(flying) < max_tracks:
+                flying.append(take())
+            outs = answer([(e[0], e[3]) for e in flying])
+            if len(outs) != len(flying):
+                raise RuntimeError(f"expected {len(flying)} outputs for the round but got {len(outs)}")
+            stepped = False
+            for k, out in enumerate(outs):
+                i, rounds, at_end, request = flying[k]
+                try:
+                    flying[k][3] = rounds.send(refiners[i]._pick(out, *request[1:], at_end))
+                    continue
+                except StopIteration:
+                    pass
+                open_groups[i] -= 1
+                if open_groups[i] == 0:
+                    steps_done[i] += 1
+                    stepped = True
+                    next_step(i)
+                flying[k] = None
+            for k in range(len(flying)):                             # a finished group's slot goes to a waiting group
+                if flying[k] is None and waiting:
+                    flying[k] = take()
+            k = 0
+            while k < len(flying):                                   # nothing waits any more: the last slot moves into a hole
+                if flying[k] is None:
+                    last = flying.pop()
+                    if k < len(flying):
+                        flying[k] = last
+                    continue
+                k += 1
+            if stepped:
+                report()
+    finally:
+        for e in flying:
+            if e is not None:
+                e[1].close()
+    return results
