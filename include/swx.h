@@ -235,6 +235,26 @@ int swx_forward_logits(swx_model *m, const int32_t *d_tokens, const int32_t *h_n
 int swx_forward_token_ranks(swx_model *m, const int32_t *d_tokens, const int32_t *h_n_tok, int W, int max_n, int n_vocab_used,
                             const void *d_xkv, float *d_prob, int32_t *d_rank, void *stream);
 
+/* the same pass reduced to what locate's greedy step reads (alignment.py:988-1010): for window w, x = the logits row
+ * swx_forward_logits defines at position h_n_tok[w] - 1, restricted to ids 0 .. eot, with x[v] = -inf for every v in d_suppress
+ * (ids outside [0, eot) in that list are ignored; d_suppress may be NULL when n_suppress == 0).
+ *  d_top  int32 [W][2]  the largest and the second-largest entry of x[0 .. eot] in the total order on (logit, index) -- the order
+ *                       of swx_forward_token_ranks; a tie goes to the higher index (the reference's unstable sort picks arbitrarily)
+ *  d_prob f32   [W][3]  p = softmax(x[0 .. eot - 1]) (EOT excluded) at { d_target[w], d_top[w][0], d_top[w][1] }; 0 where the id
+ *                       is outside [0, eot) (a target of -1, a top id equal to eot).  The arithmetic of d_token_probs.
+ * Only the last row of every window goes through the final LayerNorm and the vocabulary projection (W rows, in fixed chunks of
+ * 64 rows as in swx_forward_token_ranks: for M <= 64 the projection is one kernel on a grid that depends on n_vocab alone), and
+ * one launch of the reduction finishes all W rows: no [W][max_n][n_vocab] tensor, 5 numbers per window out.  A pass with
+ * max_n == 1 runs as a two-token pass (the token repeated; causal, so row 0 is unchanged), so that which kernels compute a window
+ * never depends on the other windows: a window's outputs do not depend on the batch it runs in.  Only enqueues.  A NaN logit is
+ * never selected (every comparison with it is false; the reference's sort ranks it highest).  Errors (nothing is launched): no
+ * weights or workspace bound (-9); a null pointer, eot <= 0, eot >= n_vocab, n_suppress < 0, a token count outside [1, max_n]
+ * (-1); max_n <= 0, a token row that is not a multiple of 16 bytes, a suppress mask beyond 48 KB of LDS (eot >= 393 184) (-2); W
+ * above the bound workspace's windows (-8). */
+int swx_forward_next_token(swx_model *m, const int32_t *d_tokens, const int32_t *h_n_tok, int W, int max_n, int eot,
+                           const int32_t *d_suppress, int n_suppress, const int32_t *d_target,
+                           const void *d_xkv, int32_t *d_top /*[W][2]*/, float *d_prob /*[W][3]*/, void *stream);
+
 /* language identification on cross-K/V that is already resident (model.detect_language without the vocabulary projection):
  * the teacher-forced pass of the single token `sot` for W windows -- the pass swx_forward_logits makes with max_n = 1, through
  * the final LayerNorm, in the bound workspace -- then, per window, x_j = dot(hidden[w], E[d_lang_tokens[j]]) (f32 accumulation
@@ -365,6 +385,11 @@ int swx_test_self_attn_multi(const void *d_q, void *d_kcache, void *d_vcache, in
  * offsets, k = 12 a bit mask of the derived forms that agreed with their shuffle form (1 wave_sum_d, 2 / 4 lane_xor16_max / 32_max,
  * 8 / 16 lane_xor16_add / 32_add, 32 wave_max, 64 wave_sum: 127 = all).  Nothing in the reference corresponds to it. */
 int swx_test_lane_xor(const uint32_t *d_in, uint32_t *d_out, int n_waves, void *stream);
+
+/* the reduction kernel of swx_forward_next_token alone, on the CALLER'S logits: d_logits f32 [W][ld] (ld > eot), the other
+ * arguments and the outputs as there.  Reads nothing past column eot of a row. */
+int swx_test_next_token_reduce(const float *d_logits, int64_t ld, int W, int eot, const int32_t *d_suppress, int n_suppress,
+                               const int32_t *d_target, int32_t *d_top, float *d_prob, void *stream);
 
 /* csrc/swx_common.h::gelu_erf2 (the GELU of the tiled / dec GEMM epilogues: two values on packed f32 instructions, both sides of
  * erff's branch) against gelu_erf (the device library's erff) over ALL 2^32 f32 bit patterns: d_out[0] = values whose results differ

@@ -712,6 +712,105 @@ __global__ __launch_bounds__(256) void token_prob_kernel(const float *__restrict
     }
 }
 
+// The greedy step of locate reduced on the device (swx_forward_next_token): one block per window.  x = logits[row][0 .. eot] with
+// the suppressed ids at -inf (a bit mask over the ids in LDS, set once per block before the passes; the passes only read it).
+// Pass 1 keeps, per thread, the two largest entries of x[0 .. eot] in the total order on (logit, index) -- token_prob_kernel's order, a
+// tie goes to the higher index -- next to the maximum of x[0 .. eot - 1]; both go through the wave butterfly (lane_xor) and a
+// four-slot LDS combine.  Pass 2 is token_prob_kernel's: the same per-thread elements of expf(x - max), the same butterfly, the
+// same combine, p = expf(x_t - max) / sum -- so on the same row the probabilities are the bits swx_score's are.  An id outside
+// [0, eot) (target -1, a top id equal to eot) has probability 0.  Nothing past column eot is read.  Dynamic LDS: (eot + 32) / 32 words.
+struct Top2 { float v1, v2; int i1, i2; };
+__device__ __forceinline__ bool top_gt(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai > bi); }
+__device__ __forceinline__ Top2 top2_merge(const Top2 &a, const Top2 &b)
+{
+    Top2 r;
+    if (top_gt(a.v1, a.i1, b.v1, b.i1)) {
+        r.v1 = a.v1; r.i1 = a.i1;
+        const bool k = top_gt(a.v2, a.i2, b.v1, b.i1);
+        r.v2 = k ? a.v2 : b.v1; r.i2 = k ? a.i2 : b.i1;
+    } else {
+        r.v1 = b.v1; r.i1 = b.i1;
+        const bool k = top_gt(a.v1, a.i1, b.v2, b.i2);
+        r.v2 = k ? a.v1 : b.v2; r.i2 = k ? a.i1 : b.i2;
+    }
+    return r;
+}
+template <int O> __device__ __forceinline__ Top2 top2_step(const Top2 &x, int lane)
+{
+    Top2 y;
+    y.v1 = lane_xor<O>(x.v1, lane); y.i1 = lane_xor<O>(x.i1, lane); y.v2 = lane_xor<O>(x.v2, lane); y.i2 = lane_xor<O>(x.i2, lane);
+    return top2_merge(x, y);
+}
+
+__global__ __launch_bounds__(256) void next_token_kernel(const float *__restrict__ logits, int64_t ld, int eot,
+                                                         const int32_t *__restrict__ suppress, int n_suppress,
+                                                         const int32_t *__restrict__ target_tok, int32_t *__restrict__ top,
+                                                         float *__restrict__ prob)
+{
+    extern __shared__ unsigned nt_mask[];
+    __shared__ float sh[4];
+    __shared__ Top2 sht[4];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const float *lg = logits + (size_t)row * ld;
+    const int n_words = (eot + 32) >> 5;                    // bits 0 .. eot
+    for (int i = tid; i < n_words; i += 256) nt_mask[i] = 0u;
+    __syncthreads();
+    for (int i = tid; i < n_suppress; i += 256) {
+        const int v = suppress[i];
+        if (v >= 0 && v < eot) atomicOr(&nt_mask[v >> 5], 1u << (v & 31));
+    }
+    __syncthreads();
+    const float ninf = -__builtin_inff();
+    auto x_at = [&](int i) { return ((nt_mask[i >> 5] >> (i & 31)) & 1u) ? ninf : lg[i]; };
+    Top2 t{ninf, ninf, -1, -2};
+    float mx = ninf;
+    for (int i = tid; i <= eot; i += 256) {
+        const float v = x_at(i);
+        if (i < eot) mx = fmaxf(mx, v);
+        if (top_gt(v, i, t.v1, t.i1)) { t.v2 = t.v1; t.i2 = t.i1; t.v1 = v; t.i1 = i; }
+        else if (top_gt(v, i, t.v2, t.i2)) { t.v2 = v; t.i2 = i; }
+    }
+    mx = wave_max(mx);
+    t = top2_step<32>(t, lane); t = top2_step<16>(t, lane); t = top2_step<8>(t, lane);
+    t = top2_step<4>(t, lane); t = top2_step<2>(t, lane); t = top2_step<1>(t, lane);
+    if (lane == 0) { sh[tid >> 6] = mx; sht[tid >> 6] = t; }
+    __syncthreads();
+    mx = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+    t = top2_merge(top2_merge(sht[0], sht[1]), top2_merge(sht[2], sht[3]));
+    __syncthreads();
+    float sum = 0.f;
+    for (int i = tid; i < eot; i += 256) sum += expf(x_at(i) - mx);
+    sum = wave_sum(sum);
+    if (lane == 0) sh[tid >> 6] = sum;
+    __syncthreads();
+    sum = sh[0] + sh[1] + sh[2] + sh[3];
+    if (tid == 0) {
+        const int ids[3] = {target_tok[row], t.i1, t.i2};
+        top[2 * row] = t.i1; top[2 * row + 1] = t.i2;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int id = ids[k];
+            prob[3 * row + k] = (id >= 0 && id < eot) ? expf(x_at(id) - mx) / sum : 0.f;
+        }
+    }
+}
+
+// rows[k] of src (row stride = n16 16-byte units) -> row k of dst: the last token row of up to 64 windows, offsets by value
+struct RowList { int32_t row[64]; };
+__global__ __launch_bounds__(256) void gather_rows_kernel(const uint4 *__restrict__ src, uint4 *__restrict__ dst, int n16, RowList rows)
+{
+    const uint4 *s = src + (size_t)rows.row[blockIdx.x] * n16;
+    uint4 *d = dst + (size_t)blockIdx.x * n16;
+    for (int i = threadIdx.x; i < n16; i += 256) d[i] = s[i];
+}
+
+// tokens [W][1] -> [W][2], the token repeated (swx_forward_next_token at max_n == 1)
+__global__ void repeat_token_kernel(const int32_t *__restrict__ in, int32_t *__restrict__ out, int W)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < 2 * W) out[idx] = in[idx >> 1];
+}
+
 __global__ void score_targets_kernel(const int32_t *__restrict__ tokens, int max_n, int n_sot, int rows_per_w,
                                      int32_t *__restrict__ targets, int total)
 {
@@ -1703,6 +1802,67 @@ int swx_forward_token_ranks(swx_model *m, const int32_t *d_tokens, const int32_t
     return 0;
 }
 
+static int next_token_reduce(const float *lg, int64_t ld, int W, int eot, const int32_t *d_suppress, int n_suppress,
+                             const int32_t *d_target, int32_t *d_top, float *d_prob, hipStream_t s)
+{
+    const size_t lds = (size_t)((eot + 32) >> 5) * sizeof(unsigned);
+    if (lds > 48 * 1024) return -2;
+    hipLaunchKernelGGL(next_token_kernel, dim3(W), dim3(256), lds, s, lg, ld, eot, d_suppress, n_suppress, d_target, d_top, d_prob);
+    SWX_CHECK_LAUNCH();
+    return 0;
+}
+
+// The teacher-forced pass of swx_forward_logits reduced on the device to what locate's greedy step reads: the two best ids of the
+// last row and three probabilities per window.  The last token row of every window is gathered out of the residual stream (row
+// offsets travel by value, 64 per launch: no upload, no host wait), so the final LayerNorm and the vocabulary projection see W
+// rows.  The projection runs in chunks of 64 rows, as in swx_forward_token_ranks: for M <= 64 the vocabulary projection is one
+// kernel on a grid that depends on N alone in both dtypes (f16: one 128-row tile; f32: one 64-row tile), and a row's dot products
+// do not depend on the other rows of its tile -- a window's logits are the same bits in any batch.  One launch of
+// next_token_kernel finishes all W rows (the logits region holds max_rows + 2 max_windows >= W rows).
+int swx_forward_next_token(swx_model *m, const int32_t *d_tokens, const int32_t *h_n_tok, int W, int max_n, int eot,
+                           const int32_t *d_suppress, int n_suppress, const int32_t *d_target, const void *d_xkv, int32_t *d_top,
+                           float *d_prob, void *stream)
+{
+    if (!m || !m->arena || !m->ws) return -9;
+    if (!d_tokens || !h_n_tok || !d_target || !d_xkv || !d_top || !d_prob || n_suppress < 0 || (n_suppress > 0 && !d_suppress)) return -1;
+    const swx_dims &D = m->dims;
+    if (eot <= 0 || eot >= D.n_vocab) return -1;
+    if (W <= 0) return 0;
+    const int d = D.n_text_state;
+    const size_t e = m->esz;
+    if (W > m->max_windows || W > m->L.logits_rows || 2 * W > SMALL_I32) return -8;
+    if (((size_t)d * e) % 16 != 0) return -2;
+    if (max_n <= 0) return -2;
+    for (int w = 0; w < W; ++w) if (h_n_tok[w] <= 0 || h_n_tok[w] > max_n) return -1;
+    hipStream_t s = S(stream);
+    int n = max_n;
+    if (max_n == 1) {
+        int32_t *two = m->Wp<int32_t>(m->L.small_i32);
+        hipLaunchKernelGGL(repeat_token_kernel, dim3(cdiv(2 * W, 256)), dim3(256), 0, s, d_tokens, two, W);
+        SWX_CHECK_LAUNCH();
+        d_tokens = two;
+        n = 2;
+    }
+    SWX_TRY(score_forward(m, d_tokens, h_n_tok, W, n, 0, 0, n, d_xkv, false, s));
+    unsigned char *x = m->ws + m->L.x, *hh = m->ws + m->L.h, *last = m->ws + m->L.att;     // att is free after the forward pass
+    const int n16 = (int)((size_t)d * e / 16);
+    for (int w0 = 0; w0 < W; w0 += 64) {
+        const int nw = (W - w0) < 64 ? (W - w0) : 64;
+        RowList rows{};
+        for (int k = 0; k < nw; ++k) rows.row[k] = (w0 + k) * n + h_n_tok[w0 + k] - 1;
+        hipLaunchKernelGGL(gather_rows_kernel, dim3(nw), dim3(256), 0, s, (const uint4 *)x, (uint4 *)(last + (size_t)w0 * d * e), n16, rows);
+        SWX_CHECK_LAUNCH();
+    }
+    SWX_TRY(swx_layernorm(m->dtype, last, d, m->A<float>(m->o_ln_g), m->A<float>(m->o_ln_b), hh, d, W, d, s));
+    float *lg = m->Wp<float>(m->L.logits);
+    const int chunk = 64;
+    for (int r0 = 0; r0 < W; r0 += chunk) {
+        const int nr = (W - r0) < chunk ? (W - r0) : chunk;
+        SWX_TRY(logits_gemm(m, hh + (size_t)r0 * d * e, d, nr, lg + (size_t)r0 * D.n_vocab, s));
+    }
+    return next_token_reduce(lg, D.n_vocab, W, eot, d_suppress, n_suppress, d_target, d_top, d_prob, s);
+}
+
 // Language identification on features that are already resident: the teacher-forced pass of the single token `sot` (the pass
 // swx_forward_logits makes with max_n = 1, through the final LayerNorm) and lang_id_kernel over the n_lang language rows of the
 // embedding -- 0.2 % of the vocabulary projection, and W * (n_lang + 1) numbers out instead of [W][n_vocab] f32.  Enqueues only:
@@ -1965,6 +2125,15 @@ int swx_test_lane_xor(const uint32_t *d_in, uint32_t *d_out, int n_waves, void *
     hipLaunchKernelGGL(lane_xor_check_kernel, dim3(n_waves), dim3(64), 0, S(stream), d_in, d_out);
     SWX_CHECK_LAUNCH();
     return 0;
+}
+
+int swx_test_next_token_reduce(const float *d_logits, int64_t ld, int W, int eot, const int32_t *d_suppress, int n_suppress,
+                               const int32_t *d_target, int32_t *d_top, float *d_prob, void *stream)
+{
+    if (!d_logits || !d_target || !d_top || !d_prob || n_suppress < 0 || (n_suppress > 0 && !d_suppress)) return -1;
+    if (eot <= 0 || ld <= eot || W < 0) return -1;
+    if (W == 0) return 0;
+    return next_token_reduce(d_logits, ld, W, eot, d_suppress, n_suppress, d_target, d_top, d_prob, S(stream));
 }
 
 int swx_test_gelu_pair(uint64_t *d_out, void *stream)

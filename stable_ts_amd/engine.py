@@ -54,6 +54,9 @@ class Engine:
     # + the language rows of the embedding); the lockstep driver of transcribe_many looks for this attribute and otherwise falls
     # back to model.detect_language per recording
     device_language_id = True
+    # forward_next_token() answers locate's greedy step on the device (swx_forward_next_token: the last row's two best ids and
+    # three probabilities per window); locate_many looks for this attribute and otherwise answers from forward_logits on the host
+    device_next_token = True
 
     def __init__(self, dims: ModelDimensions, dtype: str = "f16", device: str = "cuda:0",
                  max_windows: int = 1, max_rows: int = 5, alignment_heads: Optional[Sequence[Tuple[int, int]]] = None):
@@ -79,6 +82,7 @@ class Engine:
         self.max_windows = 0
         self.max_rows = 0
         self.ws = None
+        self._next_token_suppress = (None, None)       # forward_next_token: (suppress list, its device copy)
         self.encode_calls = 0          # device passes through the encoder / 30-s windows in them (bench.py reports both)
         self.encode_windows = 0
         self.reserve(max_windows, max_rows)
@@ -99,6 +103,7 @@ class Engine:
             e.set_alignment_heads(self._heads)
         e.max_windows, e.max_rows, e.ws = 0, 0, None
         e.encode_calls = e.encode_windows = 0
+        e._next_token_suppress = (None, None)
         e.reserve(self.max_windows if max_windows is None else max_windows, self.max_rows if max_rows is None else max_rows)
         return e
 
@@ -505,6 +510,38 @@ class Engine:
                                                _ptr(rank), self.stream), "swx_forward_token_ranks")
         return prob, rank
 
+    def forward_next_token(self, xkv: torch.Tensor, tokens: Sequence[Sequence[int]], eot: int, suppress: Sequence[int],
+                           targets: Sequence[int]) -> Tuple[np.ndarray, np.ndarray]:
+        """The greedy step of ``locate`` for W windows (``swx_forward_next_token``): with x = the logits of window w's last token
+        restricted to ids ``0 .. eot`` and the ids of ``suppress`` at -inf, ``top[w]`` = the best and the second-best id of x on
+        (logit, index) and ``prob[w]`` = ``softmax(x[:eot])`` at ``(targets[w], top[w][0], top[w][1])``, 0 for an id outside
+        ``[0, eot)`` (a target of -1).  Returns (top int32 [W, 2], prob f32 [W, 3]) on the host: one upload of tokens and targets,
+        one copy back of 20 bytes per window; the suppress list is uploaded when it changes."""
+        W = len(tokens)
+        n_tok = [len(t) for t in tokens]
+        max_n = max(n_tok)
+        if len(targets) != W:
+            raise ValueError(f"{len(targets)} targets for {W} windows")
+        if not 0 < int(eot) < self.dims.n_vocab:
+            raise ValueError(f"eot = {eot} for a vocabulary of {self.dims.n_vocab}")
+        self.reserve(max(W, self.max_windows), max(self.max_rows, 1))
+        key = tuple(int(t) for t in suppress)
+        if self._next_token_suppress[0] != key:
+            self._next_token_suppress = (key, torch.tensor(np.asarray(key or (0,), dtype=np.int32), device=self.device))
+        d_sup = self._next_token_suppress[1]
+        h_in = np.zeros(W * (max_n + 1), dtype=np.int32)
+        for w, t in enumerate(tokens):
+            h_in[w * max_n: w * max_n + len(t)] = t
+        h_in[W * max_n:] = [int(t) for t in targets]
+        d_in = torch.from_numpy(h_in).to(self.device)
+        out = torch.empty(W * 5, dtype=torch.int32, device=self.device)          # [W][2] ids | [W][3] f32 probabilities
+        at = lambda t, n: ctypes.c_void_p(t.data_ptr() + 4 * n)                  # noqa: E731
+        check(self.lib.swx_forward_next_token(self.h, at(d_in, 0), _i32arr(n_tok), W, max_n, int(eot), _ptr(d_sup), len(key),
+                                              at(d_in, W * max_n), _ptr(xkv), at(out, 0), at(out, 2 * W), self.stream),
+              "swx_forward_next_token")
+        h = out.cpu().numpy()
+        return h[: 2 * W].reshape(W, 2).copy(), h[2 * W:].view(np.float32).reshape(W, 3).copy()
+
     # ------------------------------------------------------------------ a8 dtw
     def dtw(self, x: torch.Tensor, N: Sequence[int], M: Sequence[int]):
         """x f32 device [W, ld_n, ld_m] (the NEGATED alignment matrix); returns [(text_idx, time_idx)] int64 numpy."""
@@ -516,8 +553,10 @@ def dtw(x: torch.Tensor, N: Sequence[int], M: Sequence[int]):
     assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.ndim == 3
     W, ld_n, ld_m = x.shape
     dev = x.device
-    dN = torch.tensor(np.asarray(N, dtype=np.int32), device=dev)
-    dM = torch.tensor(np.asarray(M, dtype=np.int32), device=dev)
+    # counts beyond the matrix mean the matrix's extent, as the reference's slices do (timing.py:195 `[:num_frames]`): locate()
+    # asks for the frames of up to 33 s of a 30-s window
+    dN = torch.tensor(np.minimum(np.asarray(N, dtype=np.int32), ld_n), device=dev)
+    dM = torch.tensor(np.minimum(np.asarray(M, dtype=np.int32), ld_m), device=dev)
     cap = ld_n + ld_m
     ti = torch.empty(W, cap, dtype=torch.int32, device=dev)
     tj = torch.empty(W, cap, dtype=torch.int32, device=dev)

@@ -23,6 +23,10 @@ machine of every recording (``Aligner.steps``, the generator ``Aligner.align`` i
 inference request and the requests of a round -- ragged in audio length, token count and language -- are answered by one
 ``make_alignment_func(...).batch`` call: one mel / encoder / cross-K/V / scoring / DTW job for up to ``max_tracks`` windows.
 
+``locate_many`` does it for ``locate``: the chunk state machine of every recording (``locator.LocateJob.steps``, the generator
+``locate`` itself drives) is advanced phase by phase, and the greedy steps of a round's duration windows are answered by one
+``Engine.forward_next_token`` call (``swx_forward_next_token``) instead of a vocabulary-wide logits tensor per window and step.
+
 ``refine_many`` does it for ``refine``.  ``refine(batch_size=N)`` bisects the word groups of ONE recording in lockstep, and a clip
 of a few seconds is one or two groups, so its rounds hold 2-4 windows whatever N is.  Here the groups of all recordings share
 the rounds (``stable_ts_amd.refiner.refine_tracks``: every group is the generator ``refine`` runs, a recording's steps stay in
@@ -320,3 +324,155 @@ def refine_many(model, audios: Sequence, results: Sequence[WhisperResult], *, ma
         return func.batch([(None, request[1]) for _, request in flying], resident=rows, **kw)
 
     return refine_tracks(refiners, work, max_tracks, answer, progress_callback)
+
+
+@host_single_thread
+def locate_many(model, audios: Sequence, texts: Sequence[Union[str, List[int]]], language: Union[str, Sequence[str]], *,
+                max_tracks: int = 16, device_probe: Optional[bool] = None, **locate_options) -> List[list]:
+    """``[model.locate(a, t, language=l, **locate_options) for a, t, l in zip(audios, texts, languages)]`` with the current chunk of
+    up to ``max_tracks`` recordings per device pass, in input order.  ``audios``: whatever ``locate`` takes per item; the same object
+    may appear several times (many phrases in one recording).  ``texts``: a ``str`` or token ids per recording.  ``language``: one
+    code for all, or a list with a code per recording.  Options are those of ``locate``.
+
+    Every recording runs the state machine ``locate`` runs (``locator.LocateJob.steps``); a round answers the requests of the live
+    recordings phase by phase, one device call each: (A) log-mel, encoder, cross-K/V and the scoring pass of the round's chunks,
+    (B) encoder and cross-K/V of the duration windows (modes 0 and 1), (C) the greedy steps of all these windows, ragged in
+    length, until every window has stopped -- a stopped window stays in the batch as a one-token dummy, the cross-K/V is never
+    copied between steps -- and (D) one word-timestamp job for the windows of mode 0 that confirmed their text.  A recording that
+    runs out of audio or reaches ``count`` hands its slot to the next pending one at the round boundary.
+
+    ``device_probe``: how a greedy step is answered.  True = ``Engine.forward_next_token`` (``swx_forward_next_token``: the last row
+    of every window projected on the vocabulary, two ids and three probabilities per window copied back); False = one batched
+    ``forward_logits`` call and the host arithmetic of ``locate``; None = the native call where the engine has it.  With False
+    the results are those of the loop exactly, except that a greedy step whose context was cleared to ONE token takes another
+    cross-attention kernel next to longer windows than alone (rounding-level); the native call differs from the host arithmetic
+    by rounding (probabilities within 5e-5 in log), breaks an exact tie of two logits towards the higher id and never selects a
+    NaN logit (the host sort ranks it highest).  The device
+    workspace grows to ``max_tracks`` windows and no further; the cross-K/V of a round's chunks and of its duration windows are
+    alive together (2 x ``max_tracks`` windows)."""
+    from .locator import LocateJob, _pad_frames, end_row_tokens, next_token_on_host
+    from .audio import N_FFT
+    from .timing import add_word_timestamps_batch
+    if isinstance(audios, (str, bytes)) or not hasattr(audios, "__len__") or hasattr(audios, "shape"):
+        raise TypeError("audios must be a list of recordings (locate() takes a single one)")
+    audios = list(audios)
+    if isinstance(texts, str) or not hasattr(texts, "__len__"):
+        raise TypeError("texts must be a list with one text per recording")
+    texts = list(texts)
+    if len(texts) != len(audios):
+        raise ValueError(f"texts has {len(texts)} entries for {len(audios)} recordings")
+    if max_tracks is None or isinstance(max_tracks, bool) or int(max_tracks) != max_tracks or int(max_tracks) < 1:
+        raise ValueError(f"max_tracks must be an integer of at least 1, got {max_tracks}")
+    max_tracks = int(max_tracks)
+    if language is None or isinstance(language, str):
+        languages = [language] * len(audios)
+    else:
+        languages = list(language)
+        if len(languages) != len(audios):
+            raise ValueError(f"language has {len(languages)} entries for {len(audios)} recordings")
+    eng = model.engine
+    native = bool(getattr(eng, "device_next_token", False))
+    if device_probe and not native:
+        raise RuntimeError("device_probe=True needs an engine with forward_next_token")
+    if device_probe is not None:
+        native = bool(device_probe)
+    # ---- everything that can be refused is refused here, before any recording is decoded or any device work is queued
+    jobs = [LocateJob(model, text, lang, **locate_options) for text, lang in zip(texts, languages)]
+    if not audios:
+        return []
+    n_ctx = model.dims.n_audio_ctx
+    alive: List[dict] = []                              # the device buffers of the current round
+
+    def answer(kind: str, batch: list) -> List[Any]:
+        """one device call for the requests of one phase; ``batch`` = [(recording, request)]"""
+        if kind == "chunk":
+            # the generators still hold last round's handles: empty the buffers behind them before the new ones are made, so
+            # that two cross-K/V buffers are alive at a time (this round's chunks and its duration windows), not three
+            for buffers in alive:
+                buffers.clear()
+            del alive[:]
+            mel = model.log_mel_segments([req[1] for _, req in batch], padding=N_FFT // 2 + 1)
+            whole = dict(mel=mel, xkv=model.cross_kv(model.encoder(mel)), n=len(batch))
+            alive.append(whole)
+            return [(whole, k) for k in range(len(batch))]
+        if kind == "section":
+            mel = torch.stack([_pad_frames(req[1][0]["mel"][req[1][1]][..., req[2]: req[3]]) for _, req in batch])
+            part = dict(xkv=model.cross_kv(model.encoder(mel)), n=len(batch))
+            alive.append(part)
+            return [(part, k) for k in range(len(batch))]
+        held = batch[0][1][1][0]                           # the phase's windows live in one buffer: [L][B][...] cannot be sliced
+        assert all(req[1][0] is held for _, req in batch), "requests of one phase come from one batch"
+        eot = jobs[batch[0][0]].tok.eot
+        if kind == "end_row":
+            assert [req[1][1] for _, req in batch] == list(range(held["n"]))
+            rows = [end_row_tokens(jobs[i], req[2]) for i, req in batch]
+            _, neg, _ = eng.score(held["xkv"], rows, [n_ctx] * len(rows), n_sot=0, eot=eot)
+            return [(-neg[k, len(r) - 2, :n_ctx]).float().cpu() for k, r in enumerate(rows)]
+        if kind == "next":
+            out: List[Any] = [None] * len(batch)
+            lists: dict = {}
+            for b, (i, _) in enumerate(batch):
+                lists.setdefault(tuple(jobs[i].suppressed), []).append(b)
+            # a target id outside [0, eot) is an IndexError in locate(); the kernel would answer probability 0: such a step takes
+            # the host arithmetic and raises what locate() raises
+            on_device = native and all(req[3] == -1 or 0 <= req[3] < eot for _, req in batch)
+            for suppressed, members in lists.items() if on_device else [(None, list(range(len(batch))))]:
+                tokens, targets = [[0]] * held["n"], [-1] * held["n"]          # a window that has stopped: a one-token dummy
+                for b in members:
+                    req = batch[b][1]
+                    tokens[req[1][1]], targets[req[1][1]] = req[2], req[3]
+                if on_device:
+                    top, prob = eng.forward_next_token(held["xkv"], tokens, eot, suppressed, targets)
+                    for b in members:
+                        k = batch[b][1][1][1]
+                        out[b] = (int(top[k, 0]), int(top[k, 1]), float(prob[k, 0]), float(prob[k, 1]), float(prob[k, 2]))
+                else:
+                    logits = eng.forward_logits(held["xkv"], tokens)
+                    ks = [batch[b][1][1][1] for b in members]
+                    last = torch.stack([logits[k, len(tokens[k]) - 1, : eot + 1] for k in ks]).float().cpu()
+                    for b, row in zip(members, last):
+                        i, req = batch[b]
+                        out[b] = next_token_on_host(row.clone(), eot, jobs[i].suppressed, req[3])
+            return out
+        from . import transcribe as T
+        toks = [jobs[i].tok for i, _ in batch]
+        segs = [dict(seek=0, tokens=req[2]) for _, req in batch]
+        add_word_timestamps_batch(model=model, tokenizer=toks[0] if all(t is toks[0] for t in toks) else toks,
+                                  xkv=T._xkv_select(model, held["xkv"], [req[1][1] for _, req in batch]), gap_padding=None,
+                                  windows=[dict(segments=[seg], num_samples=req[3]) for seg, (_, req) in zip(segs, batch)])
+        return [seg["words"] for seg in segs]
+
+    results: List[Optional[list]] = [None] * len(audios)
+    pending = list(range(len(audios)))
+    pending.reverse()                                   # pop() hands them out in input order
+    live: list = []                                     # [recording, generator, its open request]
+
+    def advance(i: int, steps, got=None):
+        try:
+            return steps.send(got)
+        except StopIteration as end:
+            results[i] = end.value
+            return None
+
+    try:
+        while live or pending:
+            if all(request[0] == "chunk" for _, _, request in live):       # the round boundary: free slots go to pending recordings
+                while pending and len(live) < max_tracks:
+                    i = pending.pop()
+                    steps = jobs[i].steps(jobs[i].waveform(audios[i]))
+                    request = advance(i, steps)
+                    if request is not None:
+                        live.append([i, steps, request])
+                if not live:
+                    continue
+            # everybody leaves "chunk" together, and a recording waits at its next "chunk" until nobody is in a phase of the
+            # current round any more: the phases of a round are answered in their order, "chunk" last
+            kind = next(k for k in ("end_row", "section", "next", "words", "chunk") if any(r[0] == k for _, _, r in live))
+            members = [entry for entry in live if entry[2][0] == kind]
+            for entry, got in zip(members, answer(kind, [(i, request) for i, _, request in members])):
+                entry[2] = advance(entry[0], entry[1], got)
+            live = [entry for entry in live if entry[2] is not None]
+    finally:
+        for _, steps, _ in live:
+            steps.close()
+    return results

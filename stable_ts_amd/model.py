@@ -318,10 +318,11 @@ class Whisper:
         self.locate = types.MethodType(locate, self)
         from .spans import transcribe_spans
         self.transcribe_spans = types.MethodType(transcribe_spans, self)
-        from .many import align_many, refine_many, transcribe_many
+        from .many import align_many, locate_many, refine_many, transcribe_many
         self.transcribe_many = types.MethodType(transcribe_many, self)
         self.align_many = types.MethodType(align_many, self)
         self.refine_many = types.MethodType(refine_many, self)
+        self.locate_many = types.MethodType(locate_many, self)
 
 
 def _read_checkpoint(path: str):
