@@ -380,6 +380,25 @@ int swx_test_self_attn_step(const void *d_q, void *d_kcache, void *d_vcache, con
 int swx_test_self_attn_multi(const void *d_q, void *d_kcache, void *d_vcache, int R, int H, int n_new, int n_ctx, int d, int mq,
                              void *d_o, void *stream);
 
+/* decoder self-attention over the KV cache as swx_self_attention runs it outside the single-token step (f16 or f32; dtype 1 / 0):
+ * d_qkv [R * n_new][ldqkv] with q at column 0 and, when skip_append == 0, k at column d and v at column 2 d (these are copied to
+ * position pos0[r] + i of cache row r first); logical row of grid row ri is r = ri * row_mul (caches, d_pos0 and d_anc are indexed by r);
+ * d_anc [rows][n_ctx] or NULL; pos0_all_zero: the caller states that d_pos0 holds zeros (f16 without a table then takes several tokens
+ * per workgroup from 8 tokens on); d_o [R * n_new][d].  Launches nothing and returns a negative code when n_ctx > 512, n_new > n_ctx,
+ * d != 64 H, row_mul < 1 or ldqkv < d (3 d when appending). */
+int swx_test_self_attn_general(int dtype, const void *d_qkv, int64_t ldqkv, void *d_kcache, void *d_vcache, const int32_t *d_anc,
+                               const int32_t *d_pos0, int R, int H, int n_new, int n_ctx, int d, int row_mul, int skip_append,
+                               int pos0_all_zero, void *d_o, void *stream);
+/* which kernel swx_self_attention launches (host-only, no GPU; the function the launcher itself executes): 0 self_attn_cached<f16>,
+ * 1 self_attn_cached<float>, 2 / 3 self_attn_cached_mq_f16<4 / 8>, 4 / 5 self_attn_step_f16<false> with 1 / 5 rows per workgroup,
+ * 6 / 7 self_attn_step_f16<true> with 1 / 5 rows per workgroup, 8 self_attn_step_long_f16; < 0: the call is refused.
+ * swx_test_self_attn_step's variants are step_cached = 1 with pos_bound = 128 (variant 0) or 0 (variant 1), and step_cached = 0. */
+int swx_test_self_attn_plan(int dtype, int R, int H, int n_new, int n_ctx, int row_mul, int skip_append, int step_cached, int pos_bound,
+                            int pos0_all_zero, int has_anc, int flags);
+/* which kernel swx_test_dec_gemm's launch gets (host-only, no GPU; the function swx_gemm_dec itself executes), `epilogue` as there:
+ * 0 gemm_dec_f16 with four-wave workgroups, 1 with single-wave workgroups, 2 / 3 gemm_dectall_f16 with four / eight waves; < 0: not offered */
+int swx_test_dec_plan(int M, int N, int K, int epilogue, int flags);
+
 /* the VALU lane-exchange helpers of csrc/swx_common.h (v_permlane16/32_swap, DPP) against __shfl_xor, on n_waves waves of 64
  * u32 values: d_out[((w * 13 + k) * 64) + lane], k = 0..5 lane_xor<32, 16, 8, 4, 2, 1>, k = 6..11 the __shfl_xor of the same
  * offsets, k = 12 a bit mask of the derived forms that agreed with their shuffle form (1 wave_sum_d, 2 / 4 lane_xor16_max / 32_max,

@@ -1776,39 +1776,47 @@ int swx_pad_zero(void *base, int64_t row_bytes, int64_t batch_bytes, int off_byt
     return 0;
 }
 
-int swx_self_attention(int dtype, const SelfAttnArgs &a, int row_mul, hipStream_t s)
+int swx_self_attn_plan(int dtype, const SelfAttnArgs &a, int row_mul, int flags)
 {
-    if (a.R <= 0 || a.n_new <= 0) return 0;
     if (a.n_ctx > 512) return -5;
-    // algorithmic bytes: K and V of every cached position of every row once (+ q in, o out); the positions are device state --
-    // the decode loop passes the one it knows (step_pos), multi-token passes attend to n_new positions on average n_new / 2 + 1
-    const double npos = a.step_pos > 0 ? a.step_pos + 1 : (a.n_new + 1) * 0.5;
-    SwxProfScope prof(PC_SELF_ATTN, (double)a.R * a.n_new * a.d * (dtype == SWX_F16 ? 2 : 4) * (2.0 * npos + 2.0), s);
     if (a.step_cached) {       // single-token step, q in a.qkv, the new K / V already in the cache
         if (dtype != SWX_F16 || a.n_new != 1 || row_mul != 1 || !a.skip_append) return -5;
         // (a decode whose positions stay below 128 -- no prompt carried over -- takes the variant without the long-context code:
         // 157 instead of 211 registers, three waves per SIMD)
-        const bool wg5 = (swx_flags() & SWX_FLAG_SELFATTN_WG5) != 0;       // A/B: five rows (a window's beams) per workgroup
-        if (a.pos_bound > 0 && a.pos_bound <= 128) {
-            if (wg5) hipLaunchKernelGGL((self_attn_step_f16<false, 5>), dim3(a.H, cdiv(a.R, 5)), dim3(320), 0, s, a);
-            else hipLaunchKernelGGL((self_attn_step_f16<false, 1>), dim3(a.H, a.R), dim3(64), 0, s, a);
-        } else {
-            // few waves (one window of the sequential flow: 100): every load of a row in two batches (bit-identical)
-            const bool deep = !wg5 && (int64_t)a.R * a.H <= 1024 && a.n_ctx <= 448 && !(swx_flags() & SWX_FLAG_SELFATTN_NO_DEEP);
-            if (deep) hipLaunchKernelGGL(self_attn_step_long_f16, dim3(a.H, a.R), dim3(64), 0, s, a);
-            else if (wg5) hipLaunchKernelGGL((self_attn_step_f16<true, 5>), dim3(a.H, cdiv(a.R, 5)), dim3(320), 0, s, a);
-            else hipLaunchKernelGGL((self_attn_step_f16<true, 1>), dim3(a.H, a.R), dim3(64), 0, s, a);
-        }
-        SWX_CHECK_LAUNCH();
-        return 0;
+        const bool wg5 = (flags & SWX_FLAG_SELFATTN_WG5) != 0;       // A/B: five rows (a window's beams) per workgroup
+        if (a.pos_bound > 0 && a.pos_bound <= 128) return wg5 ? SWX_SA_K_STEP_WG5 : SWX_SA_K_STEP;
+        // few waves (one window of the sequential flow: 100): every load of a row in two batches (bit-identical)
+        const bool deep = !wg5 && (int64_t)a.R * a.H <= 1024 && a.n_ctx <= 448 && !(flags & SWX_FLAG_SELFATTN_NO_DEEP);
+        return deep ? SWX_SA_K_STEP_DEEP : wg5 ? SWX_SA_K_STEP_LONG_WG5 : SWX_SA_K_STEP_LONG;
     }
+    if (dtype != SWX_F16) return SWX_SA_K_CACHED_F32;
+    // several tokens of a (row, head) per workgroup, K / V staged in LDS once (bit-identical; SWX_FLAG_SELFATTN_NO_MQ: A/B)
+    if (a.pos0_all_zero && !a.anc && a.n_new >= 8 && a.n_new <= a.n_ctx && !(flags & SWX_FLAG_SELFATTN_NO_MQ))
+        return a.n_new >= 32 ? SWX_SA_K_MQ8 : SWX_SA_K_MQ4;
+    return SWX_SA_K_CACHED_F16;
+}
+
+int swx_self_attention(int dtype, const SelfAttnArgs &a, int row_mul, hipStream_t s)
+{
+    if (a.R <= 0 || a.n_new <= 0) return 0;
+    const int kid = swx_self_attn_plan(dtype, a, row_mul, swx_flags());
+    if (kid < 0) return kid;
+    // algorithmic bytes: K and V of every cached position of every row once (+ q in, o out); the positions are device state --
+    // the decode loop passes the one it knows (step_pos), multi-token passes attend to n_new positions on average n_new / 2 + 1
+    const double npos = a.step_pos > 0 ? a.step_pos + 1 : (a.n_new + 1) * 0.5;
+    SwxProfScope prof(PC_SELF_ATTN, (double)a.R * a.n_new * a.d * (dtype == SWX_F16 ? 2 : 4) * (2.0 * npos + 2.0), s);
     dim3 g1(a.n_new, a.R);
     dim3 g2(a.n_new, a.H, a.R);
-    if (dtype == SWX_F16) {
-        if (!a.skip_append) hipLaunchKernelGGL(kv_append_kernel<f16>, g1, dim3(256), 0, s, a, row_mul);
-        // several tokens of a (row, head) per workgroup, K / V staged in LDS once (bit-identical; SWX_FLAG_SELFATTN_NO_MQ: A/B)
-        if (a.pos0_all_zero && !a.anc && a.n_new >= 8 && a.n_new <= a.n_ctx && !(swx_flags() & SWX_FLAG_SELFATTN_NO_MQ)) {
-            const int nqw = a.n_new >= 32 ? 8 : 4;
+    switch (kid) {
+        case SWX_SA_K_STEP_WG5: hipLaunchKernelGGL((self_attn_step_f16<false, 5>), dim3(a.H, cdiv(a.R, 5)), dim3(320), 0, s, a); break;
+        case SWX_SA_K_STEP: hipLaunchKernelGGL((self_attn_step_f16<false, 1>), dim3(a.H, a.R), dim3(64), 0, s, a); break;
+        case SWX_SA_K_STEP_DEEP: hipLaunchKernelGGL(self_attn_step_long_f16, dim3(a.H, a.R), dim3(64), 0, s, a); break;
+        case SWX_SA_K_STEP_LONG_WG5: hipLaunchKernelGGL((self_attn_step_f16<true, 5>), dim3(a.H, cdiv(a.R, 5)), dim3(320), 0, s, a); break;
+        case SWX_SA_K_STEP_LONG: hipLaunchKernelGGL((self_attn_step_f16<true, 1>), dim3(a.H, a.R), dim3(64), 0, s, a); break;
+        case SWX_SA_K_MQ4:
+        case SWX_SA_K_MQ8: {
+            if (!a.skip_append) hipLaunchKernelGGL(kv_append_kernel<f16>, g1, dim3(256), 0, s, a, row_mul);
+            const int nqw = kid == SWX_SA_K_MQ8 ? 8 : 4;
             const int lds_rows = ((a.n_new + 7) / 8) * 8;
             const size_t lds = (size_t)lds_rows * 72 * 2 * 2 + (size_t)nqw * 64 * 4 + (size_t)nqw * lds_rows * 4;
             dim3 gq(cdiv(a.n_new, nqw), a.H, a.R);
@@ -1829,13 +1837,17 @@ int swx_self_attention(int dtype, const SelfAttnArgs &a, int row_mul, hipStream_
                 }
                 hipLaunchKernelGGL(self_attn_cached_mq_f16<4>, gq, dim3(256), lds, s, a, row_mul, lds_rows);
             }
-            SWX_CHECK_LAUNCH();
-            return 0;
+            break;
         }
-        hipLaunchKernelGGL(self_attn_cached<f16>, g2, dim3(64), 0, s, a, row_mul);
-    } else {
-        if (!a.skip_append) hipLaunchKernelGGL(kv_append_kernel<float>, g1, dim3(256), 0, s, a, row_mul);
-        hipLaunchKernelGGL(self_attn_cached<float>, g2, dim3(64), 0, s, a, row_mul);
+        case SWX_SA_K_CACHED_F16:
+            if (!a.skip_append) hipLaunchKernelGGL(kv_append_kernel<f16>, g1, dim3(256), 0, s, a, row_mul);
+            hipLaunchKernelGGL(self_attn_cached<f16>, g2, dim3(64), 0, s, a, row_mul);
+            break;
+        case SWX_SA_K_CACHED_F32:
+            if (!a.skip_append) hipLaunchKernelGGL(kv_append_kernel<float>, g1, dim3(256), 0, s, a, row_mul);
+            hipLaunchKernelGGL(self_attn_cached<float>, g2, dim3(64), 0, s, a, row_mul);
+            break;
+        default: return -5;
     }
     SWX_CHECK_LAUNCH();
     return 0;

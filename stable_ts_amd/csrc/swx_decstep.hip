@@ -626,12 +626,40 @@ size_t swx_dec_slab_floats(int M, int N, int K)
     return ks2 > 1 ? (size_t)ks2 * M * N : 0;
 }
 
+int swx_dec_kernel_plan(int M, int N, int K, int epi_in, int tall, bool ticket_ok, int flags, int *mt_out, int *ks2_out, bool *ticket_out)
+{
+    int mt = 1, ks2 = 1;
+    { const int rc = swx_dec_plan(M, N, K, epi_in, &mt, &ks2); if (rc < 0) return rc; }
+    if (ks2 == 1 && (epi_in & DEC_SLAB)) epi_in &= ~DEC_SLAB;      // un-split after all: the kernel finishes the output itself
+    const int kslice = K / ks2, nks = kslice / 32;
+    const int units = (N / 64) * ks2;
+    const int epi = epi_in & (DEC_LN | DEC_GELU | DEC_RES | DEC_QKV | DEC_SLAB);
+    const bool use_tall = tall && M > 160 && (kslice / 32) % 4 == 0 && !(flags & SWX_FLAG_NO_TALL);
+    // SWX_FLAG_TICKET: the K-split projection of the decode-step kernel reduces its slabs inside the launch (measured slower: swx_kernels.h)
+    const bool ticket = ks2 > 1 && ks2 <= 4 && !use_tall && ticket_ok && epi == (DEC_RES | DEC_SLAB) &&
+                        (N / 64) * cdiv(M, mt * 16) <= SWX_DEC_TICKETS && (flags & SWX_FLAG_TICKET) &&
+                        N % 64 == 0;      // the kernel's early `n >= N` exit sits in front of a block barrier: whole panels only
+    *mt_out = mt; *ks2_out = ks2; *ticket_out = ticket;
+    if (use_tall) {
+        // eight waves = two panels per workgroup, from 40 (panel, K slice) units on (the un-split N = 1280 projections measured 27.4 vs 26.5 us
+        // that way: 10 double panels leave the row splits too short); bit-identical; SWX_FLAG_TALL_NO_W8: A/B
+        const bool w8 = !(flags & SWX_FLAG_TALL_NO_W8) && (N / 64) % 2 == 0 && nks % 8 == 0 && (N / 64) * ks2 >= 40;
+        return w8 ? SWX_DEC_K_TALL8 : SWX_DEC_K_TALL4;
+    }
+    // few workgroups (<= 80 of four waves: the 5 rows of a sequential window's decode step): the same waves as single-wave workgroups,
+    // spread over four times as many CUs (gemm_dec_f16<.., WPB = 1>; bit-identical; SWX_FLAG_DEC_NO_W1: A/B)
+    const bool w1 = mt == 1 && !ticket && units * cdiv(M, mt * 16) <= 80 && !(flags & SWX_FLAG_DEC_NO_W1);
+    return w1 ? SWX_DEC_K_W1 : SWX_DEC_K_W4;
+}
+
 int swx_gemm_dec(DecGemmArgs g, hipStream_t s)
 {
     if (g.M <= 0 || g.N <= 0) return 0;
     if (g.lda % 8 != 0 || ((uintptr_t)g.A & 15) || ((uintptr_t)g.W & 15)) return -4;      // g.W: packed (swx_fold_ln)
     int mt = 1, ks2 = 1;
-    { const int rc = swx_dec_plan(g.M, g.N, g.K, g.epi, &mt, &ks2); if (rc < 0) return rc; }
+    bool ticket = false;
+    const int kid = swx_dec_kernel_plan(g.M, g.N, g.K, g.epi, g.tall, g.ticket && g.X, swx_flags(), &mt, &ks2, &ticket);
+    if (kid < 0) return kid;
     if (ks2 > 1 && !g.slabs) return -4;
     if (ks2 == 1 && (g.epi & DEC_SLAB)) g.epi &= ~DEC_SLAB;      // un-split after all: the kernel finishes the output itself
     g.epi &= ~DEC_TICKET;
@@ -640,18 +668,12 @@ int swx_gemm_dec(DecGemmArgs g, hipStream_t s)
     const int nks = g.kslice / 32;
     const int units = (g.N / 64) * ks2;
     int epi = g.epi & (DEC_LN | DEC_GELU | DEC_RES | DEC_QKV | DEC_SLAB);
-    const bool use_tall = g.tall && g.M > 160 && (g.kslice / 32) % 4 == 0 && !(swx_flags() & SWX_FLAG_NO_TALL);
-    // SWX_FLAG_TICKET: the K-split projection of the decode-step kernel reduces its slabs inside the launch (measured slower: swx_kernels.h)
-    const bool ticket = ks2 > 1 && ks2 <= 4 && !use_tall && g.ticket && epi == (DEC_RES | DEC_SLAB) && g.X &&
-                        (g.N / 64) * cdiv(g.M, mt * 16) <= SWX_DEC_TICKETS && (swx_flags() & SWX_FLAG_TICKET) &&
-                        g.N % 64 == 0;      // the kernel's early `n >= N` exit sits in front of a block barrier: whole panels only
+    const bool use_tall = kid == SWX_DEC_K_TALL4 || kid == SWX_DEC_K_TALL8;
     if (ticket) epi |= DEC_TICKET;
     if (use_tall) {
         // tall kernel: ~two rounds of the chip's 256 CUs, every workgroup a run of `tps` 16-row tiles
         const int n_tiles = cdiv(g.M, 16);
-        // eight waves = two panels per workgroup, from 40 (panel, K slice) units on (the un-split N = 1280 projections measured 27.4 vs 26.5 us
-        // that way: 10 double panels leave the row splits too short); bit-identical; SWX_FLAG_TALL_NO_W8: A/B
-        const bool w8 = !(swx_flags() & SWX_FLAG_TALL_NO_W8) && (g.N / 64) % 2 == 0 && nks % 8 == 0 && (g.N / 64) * ks2 >= 40;
+        const bool w8 = kid == SWX_DEC_K_TALL8;        // eight waves = two panels per workgroup (swx_dec_kernel_plan)
         const int units = w8 ? (g.N / 128) * ks2 : (g.N / 64) * ks2;
         int rs = 512 / (cdiv(units, 8) * 8);
         if (rs < 1) rs = 1;
@@ -697,9 +719,7 @@ int swx_gemm_dec(DecGemmArgs g, hipStream_t s)
     } else {
     const int grid = cdiv(units, 8) * g.n_rg * 8;
     const size_t lds = (size_t)mt * 16 * g.kslice * 2 + (size_t)mt * 16 * sizeof(float2);
-    // few workgroups (<= 80 of four waves: the 5 rows of a sequential window's decode step): the same waves as single-wave workgroups,
-    // spread over four times as many CUs (gemm_dec_f16<.., WPB = 1>; bit-identical; SWX_FLAG_DEC_NO_W1: A/B)
-    const bool w1 = mt == 1 && !ticket && units * g.n_rg <= 80 && !(swx_flags() & SWX_FLAG_DEC_NO_W1);
+    const bool w1 = kid == SWX_DEC_K_W1;               // single-wave workgroups (swx_dec_kernel_plan)
     const int grid1 = cdiv(units * 4, 8) * g.n_rg * 8;
     g.w1_full_tile = (swx_flags() & SWX_FLAG_DEC_W1_FULL_TILE) ? 1 : 0;
     {   // (profiler scopes must not nest: each one closes the most recent record)

@@ -132,6 +132,13 @@ struct DecGemmArgs {
 int swx_dec_plan(int M, int N, int K, int epi, int *mt, int *ks2);    // <0: shape not supported by this generation
 size_t swx_dec_slab_floats(int M, int N, int K);
 int swx_gemm_dec(DecGemmArgs g, hipStream_t s);
+// which kernel swx_gemm_dec launches (pure: the function the launcher itself executes; swx_test_dec_plan).  `epi`: the DEC_* bits of the
+// call, `tall`: DecGemmArgs::tall, `ticket_ok`: a ticket buffer and X were handed in, `flags`: swx_debug_flags.  < 0: shape not offered.
+enum SwxDecKernel { SWX_DEC_K_W4 = 0,        // gemm_dec_f16, four-wave workgroups (1-3 row tiles per workgroup)
+                    SWX_DEC_K_W1 = 1,        // gemm_dec_f16, single-wave workgroups
+                    SWX_DEC_K_TALL4 = 2,     // gemm_dectall_f16, four waves = one panel per workgroup
+                    SWX_DEC_K_TALL8 = 3 };   // gemm_dectall_f16, eight waves = two panels per workgroup
+int swx_dec_kernel_plan(int M, int N, int K, int epi, int tall, bool ticket_ok, int flags, int *mt, int *ks2, bool *ticket);
 // load-time LayerNorm fold + re-pack into MFMA fragment order: Wf = pack(f16(W * gamma)), c1[n] = sum_k Wf[n][k],
 // c2[n] = bias[n] + sum_k beta[k] W[n][k];  gamma == null: plain re-pack of W (c1 / c2 untouched)
 int swx_fold_ln(const void *W, const float *gamma, const float *beta, const float *bias, void *Wf, float *c1, float *c2,
@@ -216,6 +223,18 @@ struct SelfAttnArgs {
 };
 // logical row of grid index ri is ri * row_mul (prefill of beam groups computes one row per window)
 int swx_self_attention(int dtype, const SelfAttnArgs &a, int row_mul, hipStream_t s);
+// which kernel swx_self_attention launches for these arguments (pure: the function the launcher itself executes; swx_test_self_attn_plan).
+// Reads the scalar fields of `a` and whether a.anc is set, no memory.  `flags`: swx_debug_flags.  < 0: the error swx_self_attention returns.
+enum SwxSelfAttnKernel { SWX_SA_K_CACHED_F16 = 0,      // self_attn_cached<f16> (after kv_append_kernel<f16> unless skip_append)
+                         SWX_SA_K_CACHED_F32 = 1,      // self_attn_cached<float> (the same)
+                         SWX_SA_K_MQ4 = 2,             // self_attn_cached_mq_f16<4>
+                         SWX_SA_K_MQ8 = 3,             // self_attn_cached_mq_f16<8>
+                         SWX_SA_K_STEP = 4,            // self_attn_step_f16<false, 1>
+                         SWX_SA_K_STEP_WG5 = 5,        // self_attn_step_f16<false, 5>
+                         SWX_SA_K_STEP_LONG = 6,       // self_attn_step_f16<true, 1>
+                         SWX_SA_K_STEP_LONG_WG5 = 7,   // self_attn_step_f16<true, 5>
+                         SWX_SA_K_STEP_DEEP = 8 };     // self_attn_step_long_f16
+int swx_self_attn_plan(int dtype, const SelfAttnArgs &a, int row_mul, int flags);
 // raw scaled qk of selected heads: out[w][hi][i][f] = 0.125 * q[w][row0+i][head] . k[w][f][head]
 int swx_qk_capture(int dtype, const void *q, int64_t ldq, int q_rows_per_w, int row0, int n_rows, const void *k,
                    int64_t ldk, int64_t k_bs, int nk, const int32_t *heads, int n_heads, int head_slot0, int slots_total, int W,

@@ -2103,6 +2103,40 @@ int swx_test_self_attn_multi(const void *d_q, void *d_kcache, void *d_vcache, in
     return swx_self_attention(SWX_F16, sa, 1, S(stream));
 }
 
+int swx_test_self_attn_general(int dtype, const void *d_qkv, int64_t ldqkv, void *d_kcache, void *d_vcache, const int32_t *d_anc,
+                               const int32_t *d_pos0, int R, int H, int n_new, int n_ctx, int d, int row_mul, int skip_append,
+                               int pos0_all_zero, void *d_o, void *stream)
+{
+    if (dtype != SWX_F16 && dtype != SWX_F32) return -1;
+    if (!d_qkv || !d_kcache || !d_vcache || !d_pos0 || !d_o) return -1;
+    if (R <= 0 || H <= 0 || n_new <= 0 || n_ctx <= 0 || n_ctx > 512 || n_new > n_ctx || d != 64 * H || row_mul < 1) return -2;
+    if (ldqkv < (skip_append ? d : 3 * d)) return -2;
+    SelfAttnArgs sa{};
+    sa.qkv = d_qkv; sa.ldqkv = ldqkv; sa.kcache = d_kcache; sa.vcache = d_vcache; sa.anc = (int32_t *)d_anc; sa.pos0 = d_pos0;
+    sa.o = d_o; sa.ldo = d; sa.R = R; sa.n_new = n_new; sa.H = H; sa.n_ctx = n_ctx; sa.d = d; sa.skip_append = skip_append ? 1 : 0;
+    sa.pos0_all_zero = pos0_all_zero ? 1 : 0;
+    return swx_self_attention(dtype, sa, row_mul, S(stream));
+}
+
+int swx_test_self_attn_plan(int dtype, int R, int H, int n_new, int n_ctx, int row_mul, int skip_append, int step_cached, int pos_bound,
+                            int pos0_all_zero, int has_anc, int flags)
+{
+    static int32_t some_table;                   // only whether a.anc is set matters to the plan
+    SelfAttnArgs sa{};
+    sa.anc = has_anc ? &some_table : nullptr;
+    sa.R = R; sa.n_new = n_new; sa.H = H; sa.n_ctx = n_ctx; sa.d = 64 * H; sa.skip_append = skip_append;
+    sa.step_cached = step_cached; sa.pos_bound = pos_bound; sa.pos0_all_zero = pos0_all_zero;
+    return swx_self_attn_plan(dtype, sa, row_mul, flags);
+}
+
+int swx_test_dec_plan(int M, int N, int K, int epilogue, int flags)
+{
+    // `epilogue` as swx_test_dec_gemm reads it (bit 6: a multi-token pass); the hook hands in a ticket buffer always and X with bit 2
+    int mt = 1, ks2 = 1;
+    bool ticket = false;
+    return swx_dec_kernel_plan(M, N, K, epilogue & 31, (epilogue & 64) ? 1 : 0, (epilogue & DEC_RES) != 0, flags, &mt, &ks2, &ticket);
+}
+
 int swx_test_layernorm(int dtype, const void *d_x, const float *d_g, const float *d_b, void *d_y, int rows, int d, void *stream)
 {
     return swx_layernorm(dtype, d_x, d, d_g, d_b, d_y, d, rows, d, S(stream));

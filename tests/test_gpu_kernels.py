@@ -251,18 +251,35 @@ def test_gemm_epilogues():
 
 
 @pytest.mark.parametrize("dtype", [0, 1])
-def test_layernorm(dtype):
+@pytest.mark.parametrize("rows", [1, 4, 5, 301])
+@pytest.mark.parametrize("d", [384, 512, 768, 1024, 1280])
+def test_layernorm(dtype, rows, d):
+    # one wave per row, four rows per workgroup, the row in up to three 512-element chunks per lane (d = 1280: the third one partial);
+    # rows 1 / 5 leave waves of a workgroup idle.  Rows differ in scale (0.1 .. 10) and offset (-4 .. 4) so that the statistics matter.
+    # Reference: float64 on the values as stored.  Tolerance relative to max |ref|: 2e-5 (f32 statistics and arithmetic; an f32
+    # restatement of the kernel on these inputs stays at 3.6e-7) / 2e-3 (f16: the rounding of the output, 4.1e-4 there)
     lib = _lib()
     tdt = torch.float16 if dtype else torch.float32
-    g = torch.Generator().manual_seed(4)
-    x = (torch.randn(301, 384, generator=g) * 3 + 1).to(tdt).cuda()
-    gam = torch.randn(384, generator=g).cuda()
-    bet = torch.randn(384, generator=g).cuda()
-    y = torch.empty_like(x)
-    assert lib.swx_test_layernorm(dtype, _p(x), _p(gam), _p(bet), _p(y), 301, 384, _stream()) == 0
-    ref = torch.nn.functional.layer_norm(x.float(), (384,), gam, bet, 1e-5)
+    g = torch.Generator().manual_seed(4 + rows * 7 + d)
+    s_row = 10.0 ** (torch.rand(rows, 1, generator=g) * 2 - 1)
+    o_row = torch.rand(rows, 1, generator=g) * 8 - 4
+    x = (torch.randn(rows, d, generator=g) * s_row + o_row).to(tdt).cuda()
+    gam = torch.randn(d, generator=g).cuda()
+    bet = torch.randn(d, generator=g).cuda()
+    guard = 4                                                    # rows past the last one: must stay untouched
+    y = torch.full((rows + guard, d), float("nan"), dtype=tdt, device="cuda")
+    assert lib.swx_test_layernorm(dtype, _p(x), _p(gam), _p(bet), _p(y), rows, d, _stream()) == 0
+    torch.cuda.synchronize()
+    x64 = x.double().cpu()
+    mu = x64.mean(1, keepdim=True)
+    var = ((x64 - mu) ** 2).mean(1, keepdim=True)
+    ref = (x64 - mu) / torch.sqrt(var + 1e-5) * gam.double().cpu() + bet.double().cpu()
+    got = y.cpu()
+    assert not torch.isnan(got[:rows]).any() and torch.isnan(got[rows:]).all()      # exactly rows x d elements are written
     tol = 2e-3 if dtype else 2e-5
-    assert (y.float() - ref).abs().max().item() < tol * ref.abs().max().item()
+    err = (got[:rows].double() - ref).abs().max().item()
+    print(f"layernorm dtype={dtype} rows={rows} d={d}: max error / max|ref| = {err / ref.abs().max().item():.3g}")
+    assert err < tol * ref.abs().max().item(), (err, ref.abs().max().item())
 
 
 # --------------------------------------------------------------------------------------------------- attention
@@ -459,9 +476,11 @@ def _dec_scratch_bytes(M, N, K):
     return N * K * 2 + 8 * N + 16 * M * N * 4 + 8192 + 4096 * 4
 
 
-def _dec_gemm(a, w, *, gamma=None, beta=None, bias=None, x=None, epi=0, d=0, n_ctx=0, pos0=None, scratch=None):
+def _dec_gemm(a, w, *, gamma=None, beta=None, bias=None, x=None, epi=0, d=0, n_ctx=0, pos0=None, scratch=None, cache_rows=None):
     """calls swx_test_dec_gemm; returns dict(c=..., x=..., kcache=..., vcache=...) as CPU float32 arrays.  ``scratch``: a zeroed
-    buffer the caller keeps over several calls (epi bit 128: the library then leaves the arrival counters as the last launch left them)"""
+    buffer the caller keeps over several calls (epi bit 128: the library then leaves the arrival counters as the last launch left them).
+    epi bit 64: a multi-token pass (the tall kernel from 161 rows on); with the QKV scatter its rows are 7 tokens per sequence, ``pos0``
+    holds one start position per sequence and the caches have ``cache_rows`` rows (one per sequence)"""
     lib = _lib()
     M, K = a.shape
     N = w.shape[0]
@@ -475,9 +494,10 @@ def _dec_gemm(a, w, *, gamma=None, beta=None, bias=None, x=None, epi=0, d=0, n_c
     tx = None if x is None else torch.from_numpy(x).to(dev).half().contiguous()
     kc = vc = tp = None
     if epi & 8:
-        kc = torch.zeros(M, n_ctx, d, dtype=torch.float16, device=dev)
-        vc = torch.zeros(M, n_ctx, d, dtype=torch.float16, device=dev)
+        kc = torch.zeros(cache_rows or M, n_ctx, d, dtype=torch.float16, device=dev)
+        vc = torch.zeros(cache_rows or M, n_ctx, d, dtype=torch.float16, device=dev)
         tp = torch.from_numpy(np.asarray(pos0, np.int32)).to(dev)
+        assert len(pos0) == (cache_rows or M) and ((epi & 64) != 0) == (cache_rows is not None)
     if scratch is None:
         scratch = torch.empty(_dec_scratch_bytes(M, N, K), dtype=torch.uint8, device=dev)
     rc = lib.swx_test_dec_gemm(_p(ta), K, _p(tw), None if tg is None else _p(tg), None if tb is None else _p(tb), _p(tbias),
@@ -625,6 +645,94 @@ def test_dec_gemm_qkv_scatter(M, d):
         mask = np.ones(n_ctx, bool)
         mask[pos0[m]] = False
         assert (got["kcache"][m, mask] == 0).all() and (got["vcache"][m, mask] == 0).all()      # nothing else is touched
+
+
+# -------------------------------------------------------------------------------------------- tall dec GEMM
+# gemm_dectall_f16 runs every projection of a multi-token pass from 161 rows on (register-resident weights, 16-row tiles, LDS-DMA
+# from inline asm).  tests/hw_checks/dec_tall_check.py compares it with gemm_dec_f16 bit for bit, both launches on the same
+# row -> (sequence, token) -> cache-position map; here the f64 reference states the operation and the map on their own.
+# M: a one-row tail tile, an exact multiple of 16, one row over, several tiles per workgroup; the two last shapes meet the conditions
+# of the eight-wave form.  Epilogue bits: LN 1, GELU 2, RES 4, QKV 8, SLAB 16.
+_TALL_CASES = [(M, N, K, epi) for M in (161, 176, 177, 333)
+               for N, K, epi in ((384, 384, 1), (1152, 384, 1 | 8), (1536, 384, 1 | 2), (384, 384, 4), (384, 1536, 4 | 16))]
+_TALL_W8_CASES = [(200, 3072, 1024, 1 | 8), (161, 1280, 5120, 4 | 16)]
+_DEC_W4, _DEC_W1, _DEC_TALL4, _DEC_TALL8 = range(4)
+_TALL, _NO_TALL, _TALL_NO_W8 = 64, 524288, 32
+
+
+@pytest.mark.parametrize("M,N,K,epi", _TALL_CASES + _TALL_W8_CASES)
+def test_dec_gemm_tall_against_f64_and_the_decode_step_kernel(M, N, K, epi):
+    lib = _lib()
+    w8 = (M, N, K, epi) in _TALL_W8_CASES
+    rng = np.random.default_rng(M * 11 + N + K + epi)
+    w = rng.standard_normal((N, K)).astype(np.float32) * 0.03
+    b = rng.standard_normal(N).astype(np.float32) * 0.1
+    kw, ref, n_ctx, d = dict(epi=epi | _TALL), {}, 32, 0
+    if epi & 4:           # x += a W^T + b: the inputs and the tolerance of test_dec_gemm_residual
+        a = rng.standard_normal((M, K)).astype(np.float32) * 0.5
+        x = rng.standard_normal((M, N)).astype(np.float32)
+        kw.update(bias=b, x=x)
+        ref["x"] = _h(x) + b.astype(np.float64) + _h(a) @ _h(w).T
+    else:
+        gamma = (1.0 + 0.2 * rng.standard_normal(K)).astype(np.float32)
+        beta = (0.1 * rng.standard_normal(K)).astype(np.float32)
+        if epi & 8:       # the inputs of test_dec_gemm_qkv_scatter; rows are 7 tokens per sequence
+            d = N // 3
+            assert d == K
+            a = rng.standard_normal((M, K)).astype(np.float32)
+            b[d:2 * d] = 0.0
+            n_seq = (M + 6) // 7
+            pos0 = rng.integers(0, n_ctx - 6, n_seq)
+            pos0[0], pos0[-1] = 0, n_ctx - 7                     # both ends of the context
+            kw.update(d=d, n_ctx=n_ctx, pos0=pos0, cache_rows=n_seq)
+        else:             # the inputs of test_dec_gemm_layernorm_fold
+            a = (rng.standard_normal((M, K)) * rng.uniform(0.5, 4.0, (M, 1)) + rng.uniform(-2, 2, (M, 1))).astype(np.float32)
+        kw.update(gamma=gamma, beta=beta, bias=b)
+        ah = _h(a)
+        ln = (ah - ah.mean(1, keepdims=True)) / np.sqrt(ah.var(1, keepdims=True) + 1e-5) * gamma.astype(np.float64) + beta.astype(np.float64)
+        full = ln @ _h(w).T + b.astype(np.float64)
+        if epi & 2:
+            full = _gelu64(full)
+        if epi & 8:
+            # the scatter, stated on its own: row m is token m % 7 of sequence m // 7 and lands at position pos0[m // 7] + m % 7 of
+            # that sequence's cache row -- and nowhere else
+            ref["c"] = full[:, :d]
+            ref["kcache"], ref["vcache"] = np.zeros((n_seq, n_ctx, d)), np.zeros((n_seq, n_ctx, d))
+            written = np.zeros((n_seq, n_ctx), bool)
+            for m in range(M):
+                ref["kcache"][m // 7, pos0[m // 7] + m % 7] = full[m, d:2 * d]
+                ref["vcache"][m // 7, pos0[m // 7] + m % 7] = full[m, 2 * d:]
+                written[m // 7, pos0[m // 7] + m % 7] = True
+            assert written.sum() == M
+        else:
+            ref["c"] = full
+    prev = lib.swx_debug_flags(-1)
+    base = prev & ~(_NO_TALL | _TALL_NO_W8)
+    runs = [(0, _DEC_TALL8 if w8 else _DEC_TALL4)] + ([(_TALL_NO_W8, _DEC_TALL4)] if w8 else []) + [(_NO_TALL, None)]
+    outs = []
+    try:
+        for flags, want in runs:
+            kid = lib.swx_test_dec_plan(M, N, K, epi | _TALL, base | flags)
+            assert kid == want if want is not None else kid in (_DEC_W4, _DEC_W1), (flags, kid)
+            lib.swx_debug_flags(base | flags)
+            outs.append(_dec_gemm(a, w, **kw))
+            lib.swx_debug_flags(prev)
+    finally:
+        lib.swx_debug_flags(prev)
+    for got in outs[:-1]:
+        for key, r in ref.items():
+            err = np.abs(got[key] - r)
+            if epi & 4:
+                assert (err <= 2e-3 * np.maximum(1.0, np.abs(r)) + 1e-3).all(), (key, float(err.max()))
+            elif epi & 8:
+                assert err.max() < 3e-2, (key, float(err.max()))
+                if key != "c":
+                    assert (got[key][~written] == 0).all(), key                           # nothing else is touched
+                    assert (got[key][written] != 0).any(axis=-1).all(), key
+            else:
+                assert err.max() < 3e-2 and err.mean() < 2e-3, (key, float(err.max()), float(err.mean()))
+            # ... and the bits of the decode-step kernel on the same call (SWX_FLAG_NO_TALL)
+            assert np.array_equal(got[key], outs[-1][key]), (key, float(np.abs(got[key] - outs[-1][key]).max()))
 
 
 # ------------------------------------------------------------------------------------- silence analysis, device half
