@@ -389,6 +389,29 @@ int swx_test_self_attn_multi(const void *d_q, void *d_kcache, void *d_vcache, in
 int swx_test_self_attn_general(int dtype, const void *d_qkv, int64_t ldqkv, void *d_kcache, void *d_vcache, const int32_t *d_anc,
                                const int32_t *d_pos0, int R, int H, int n_new, int n_ctx, int d, int row_mul, int skip_append,
                                int pos0_all_zero, void *d_o, void *stream);
+/* ---- layout of the decoder self-attention K cache (csrc/swx_kernels.h: KLayout).  A cache row is n_ctx * d elements; inside it
+ * element (pos, h, dim) lies at (pos * H + h) * 64 + dim when row-major and at ((h * 8 + dim / 8) * n_ctx + pos) * 8 + dim % 8 when
+ * chunked (k_chunked != 0: what the f16 decode engine keeps when swx_debug_flags bit 2 is set; A/B).  The V cache is row-major always.
+ * swx_test_kcache_index: the library's own index function, host-only: element offset of dims 8 chunk .. 8 chunk + 7 of head h at pos
+ * (< 0: arguments out of range).  swx_test_kcache_relayout: HOST buffers of `rows` cache rows, row-major -> chunked (to_chunked != 0)
+ * or back, through the same function; src and dst must not overlap.
+ * The *_kl calls are the test entry points of the same names with the layout of d_kcache as an argument (f16 only when chunked):
+ *   swx_test_dec_gemm_kl        also rps > 0: rows per sequence of the QKV scatter (row m = sequence m / rps, token m % rps)
+ *   swx_test_self_attn_general_kl  also step_variant: 0 the multi-token kernels; 1 / 2: n_new == 1 through the decode-step kernels with
+ *                                  the position bound 128 / unknown (the long-context kernels) */
+int swx_test_kcache_index(int k_chunked, int n_ctx, int d, int pos, int h, int chunk);
+int swx_test_kcache_relayout(const void *h_src, void *h_dst, int64_t rows, int n_ctx, int d, int elem_bytes, int to_chunked);
+int swx_test_dec_gemm_kl(const void *d_a, int64_t lda, const void *d_w, const float *d_gamma, const float *d_beta,
+                         const float *d_bias, void *d_c, int64_t ldc, void *d_x, void *d_kcache, void *d_vcache,
+                         const int32_t *d_pos0, int n_ctx, int d, int M, int N, int K, int epilogue, int rps, int k_chunked,
+                         void *d_scratch, size_t scratch_bytes, void *stream);
+int swx_test_self_attn_step_kl(const void *d_q, void *d_kcache, void *d_vcache, const int32_t *d_anc, const int32_t *d_pos0,
+                               int R, int H, int n_ctx, int d, int variant, int k_chunked, void *d_o, void *stream);
+int swx_test_self_attn_multi_kl(const void *d_q, void *d_kcache, void *d_vcache, int R, int H, int n_new, int n_ctx, int d, int mq,
+                                int k_chunked, void *d_o, void *stream);
+int swx_test_self_attn_general_kl(int dtype, const void *d_qkv, int64_t ldqkv, void *d_kcache, void *d_vcache, const int32_t *d_anc,
+                                  const int32_t *d_pos0, int R, int H, int n_new, int n_ctx, int d, int row_mul, int skip_append,
+                                  int pos0_all_zero, int step_variant, int k_chunked, void *d_o, void *stream);
 /* which kernel swx_self_attention launches (host-only, no GPU; the function the launcher itself executes): 0 self_attn_cached<f16>,
  * 1 self_attn_cached<float>, 2 / 3 self_attn_cached_mq_f16<4 / 8>, 4 / 5 self_attn_step_f16<false> with 1 / 5 rows per workgroup,
  * 6 / 7 self_attn_step_f16<true> with 1 / 5 rows per workgroup, 8 self_attn_step_long_f16; < 0: the call is refused.

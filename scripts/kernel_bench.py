@@ -1,6 +1,6 @@
 """Per-kernel micro-benchmarks at the bench workload's shapes (large-v3, 20 windows x beam 5) through libswx's test hooks.
 
-    python scripts/kernel_bench.py [--iters 200] [--only gemm|gemm_small|gemm_big|flash|flash_small|cross|dec|dtw]
+    python scripts/kernel_bench.py [--iters 200] [--only gemm|gemm_small|gemm_big|flash|flash_small|cross|dec|dtw|self_step]
 
 One HIP-event pair brackets `iters` back-to-back launches of the same kernel, so the figure is the steady-state
 launch-to-launch time (kernel + one kernel boundary), which is what a dependent chain such as the decode step pays.
@@ -227,6 +227,58 @@ def main():
                 continue
             us = timed(fn2, args.iters)
             print(f"  dec     M={M:4d} N={N}: {us:7.2f} us  {2.0 * N * K / us / 1e3:7.1f} GB/s of weights")
+
+    if args.only in ("self_step",):
+        # decode-step self-attention at the headline shape (100 rows = 20 windows x beam 5, large-v3) on both K cache layouts, alternating.
+        # The caches of `L` "layers" are rotated so that no launch finds its bytes in the 256 MB Infinity Cache: L = 32, or as many as it takes
+        # to put > 300 MB of touched lines between two launches on one layer (a launch at position 8 touches 4.6 MB).  A row's older
+        # positions come from random rows of its window (ancestor table), as in a beam search.
+        R, H, d, n_ctx = 100, 20, 1280, 448
+        print(f"-- decode-step self-attention self_attn_step_f16<false,1>, R={R} H={H} d={d} n_ctx={n_ctx}, ancestor table, caches rotated")
+        q = rnd(R, d)
+        o = torch.empty(R, d, dtype=torch.half, device=dev)
+        own = torch.arange(R, device=dev)[:, None].expand(R, n_ctx)
+        # ancestor tables: every older position from a RANDOM beam of the window (no two neighbouring keys share a cache row: the worst case
+        # of the chunked layout, whose contiguous runs end where the ancestor changes) and every position from the row itself (the best)
+        for anc_name, anc in (("random beam", (own // 5 * 5 + torch.randint(0, 5, (R, n_ctx), device=dev)).int().contiguous()),
+                              ("own row", own.int().contiguous())):
+            print(f"  ancestors: {anc_name}")
+            for pos in (8, 56, 111):
+                L = max(32, int(300e6 / (R * (pos + 1) * d * 4)) + 1)
+                kc = torch.zeros(L, R, n_ctx, d, dtype=torch.half, device=dev)
+                vc = torch.zeros(L, R, n_ctx, d, dtype=torch.half, device=dev)
+                kc.normal_(std=0.05)          # (the whole row: either layout then reads numbers wherever positions 0 .. pos lie in it)
+                vc[:, :, :pos + 1].normal_(std=0.05)
+                pos0 = torch.full((R,), pos, dtype=torch.int32, device=dev)
+                # one captured graph of n chained launches per layout (a Python loop cannot issue 4-us kernels as fast as they retire)
+                n = max(args.iters, 2 * L)
+                kps, vps = [p(kc[i]) for i in range(L)], [p(vc[i]) for i in range(L)]
+                graphs = {}
+                for ch in (0, 1):
+                    assert lib.swx_test_self_attn_step_kl(p(q), kps[0], vps[0], p(anc), p(pos0), R, H, n_ctx, d, 0, ch, p(o), st) == 0
+                    torch.cuda.synchronize()
+                    graphs[ch] = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graphs[ch]):
+                        cs = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                        for i in range(n):
+                            rc = lib.swx_test_self_attn_step_kl(p(q), kps[i % L], vps[i % L], p(anc), p(pos0), R, H, n_ctx, d, 0, ch, p(o), cs)
+                            assert rc == 0, rc
+                res = {0: [], 1: []}
+                for rep in range(4):
+                    for ch in (0, 1):
+                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record()
+                        graphs[ch].replay()
+                        b.record()
+                        torch.cuda.synchronize()
+                        if rep:                       # (the first replay of each is the warm-up)
+                            res[ch].append(a.elapsed_time(b) * 1000.0 / n)
+                del graphs
+                mb = R * (pos + 1) * d * 4 / 1e6
+                fmt = lambda v: " ".join(f"{x:6.2f}" for x in v)
+                print(f"  pos {pos:3d} ({mb:5.1f} MB, {L} layers): row-major {fmt(res[0])} us | chunked {fmt(res[1])} us | "
+                      f"min {min(res[0]):6.2f} vs {min(res[1]):6.2f}")
+                del kc, vc
 
     if args.only in ("", "dtw"):
         print("-- DTW + backtrace (one workgroup per window)")

@@ -111,6 +111,17 @@ SYMBOLS = {
     "swx_test_self_attn_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "swx_test_self_attn_general": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                            c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "swx_test_kcache_index": (c_int, [c_int] * 6),
+    "swx_test_kcache_relayout": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int]),
+    "swx_test_dec_gemm_kl": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                     c_size_t, c_void_p]),
+    "swx_test_self_attn_step_kl": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                           c_void_p, c_void_p]),
+    "swx_test_self_attn_multi_kl": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                            c_void_p]),
+    "swx_test_self_attn_general_kl": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                              c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "swx_test_self_attn_plan": (c_int, [c_int] * 12),
     "swx_test_dec_plan": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "swx_test_gelu_pair": (c_int, [c_void_p, c_void_p]),

@@ -1049,14 +1049,29 @@ __global__ __launch_bounds__(256) void kv_append_kernel(SelfAttnArgs a, int row_
     const int r = ri * row_mul;
     const int pos = a.pos0[r] + i;
     const T *src = (const T *)a.qkv + ((size_t)ri * a.n_new + i) * a.ldqkv;
-    T *kc = (T *)a.kcache + ((size_t)r * a.n_ctx + pos) * a.d;
+    T *kc = (T *)a.kcache + (size_t)r * a.n_ctx * a.d;
     T *vc = (T *)a.vcache + ((size_t)r * a.n_ctx + pos) * a.d;
-    for (int c = threadIdx.x; c < a.d; c += 256) { kc[c] = src[a.d + c]; vc[c] = src[2 * a.d + c]; }
+    for (int c = threadIdx.x; c < a.d; c += 256) { kc[swx_kidx(a.kl, pos, c >> 6, (c >> 3) & 7) + (c & 7)] = src[a.d + c]; vc[c] = src[2 * a.d + c]; }
 }
 
-template <typename T>
+// CH (all readers below): the K cache rows are chunked (a.kl, swx_kernels.h: KLayout); false: row-major, the strides are the
+// compile-time ones (sc = 8 elements -> the eight 16-byte loads of a key are one address + immediate offsets)
+template <bool CH>
+__device__ __forceinline__ KLayout k_layout_of(KLayout kl, int d) { return CH ? kl : KLayout{d, DH, 8}; }
+
+// first element of head h's key at `pos` of cache row `row`.  Row-major, a position is one more "row" of d elements: the address is formed as
+// ((row * n_ctx + pos) * d + head offset), one 64-bit multiply, which is what keeps the step kernels at their register counts
+template <bool CH, typename T>
+__device__ __forceinline__ const T *k_key_ptr(const T *kc, int n_ctx, int d, KLayout kl, int row, int pos, int h)
+{
+    if (CH) return kc + (size_t)row * n_ctx * d + swx_kidx(kl, pos, h, 0);
+    return kc + ((size_t)row * n_ctx + pos) * d + swx_kidx(kl, 0, h, 0);
+}
+
+template <typename T, bool CH = false>
 __global__ __launch_bounds__(64) void self_attn_cached(SelfAttnArgs a, int row_mul)
 {
+    const KLayout kl = k_layout_of<CH>(a.kl, a.d);
     // grid (n_new, H, R): one wave per (row, new token, head); causal over positions [0, pos0 + i]
     __shared__ float qs[DH];
     __shared__ float ps[512];
@@ -1071,12 +1086,12 @@ __global__ __launch_bounds__(64) void self_attn_cached(SelfAttnArgs a, int row_m
     float mx = -__builtin_inff();
     for (int j = lane; j <= pos; j += 64) {
         const int pr = anc ? anc[j] : r;
-        const T *kr = (const T *)a.kcache + ((size_t)pr * a.n_ctx + j) * a.d + h * DH;
+        const T *kr = k_key_ptr<CH>((const T *)a.kcache, a.n_ctx, a.d, kl, pr, j, h);
         float acc = 0.f;
 #pragma unroll 2
         for (int d0 = 0; d0 < DH; d0 += 8) {
             float kv[8];
-            load8<T>(kr + d0, kv);
+            load8<T>(kr + (d0 >> 3) * kl.sc, kv);
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc = fmaf(qs[d0 + e], kv[e], acc);
         }
@@ -1124,9 +1139,10 @@ __global__ __launch_bounds__(64) void self_attn_cached(SelfAttnArgs a, int row_m
 // wave's 16-byte reads fall on 64 different banks) and every wave runs self_attn_cached's arithmetic on its own token from there -- per score the
 // same fmaf chain over d, the same expf, per output element the same key order per lane group and the same lane reduction: bit-identical
 // (tests/test_gpu_kernels.py).  f16, no ancestor table, rows that start at position 0 (teacher-forced passes and prefills: the host knows it).
-template <int NQW>
+template <int NQW, bool CH = false>
 __global__ __launch_bounds__(64 * NQW) void self_attn_cached_mq_f16(SelfAttnArgs a, int row_mul, int lds_rows)
 {
+    const KLayout kl = k_layout_of<CH>(a.kl, a.d);
     extern __shared__ __attribute__((aligned(16))) unsigned char mq_smem[];   // K [lds_rows][72] | V [lds_rows][72] f16 | qs [NQW][64] | ps [NQW][lds_rows] f32
     constexpr int LD = 72;
     f16 *Ks = (f16 *)mq_smem, *Vs = Ks + (size_t)lds_rows * LD;
@@ -1136,11 +1152,11 @@ __global__ __launch_bounds__(64 * NQW) void self_attn_cached_mq_f16(SelfAttnArgs
     const int r = ri * row_mul;
     const int i_last = (i0 + NQW < a.n_new ? i0 + NQW : a.n_new) - 1;       // rows start at position 0: token i attends to positions 0 .. i
     {
-        const f16 *kg_ = (const f16 *)a.kcache + (size_t)r * a.n_ctx * a.d + h * DH;
+        const f16 *kg_ = (const f16 *)a.kcache + (size_t)r * a.n_ctx * a.d;
         const f16 *vg_ = (const f16 *)a.vcache + (size_t)r * a.n_ctx * a.d + h * DH;
         for (int c = tid; c < (i_last + 1) * 8; c += 64 * NQW) {
             const int j = c >> 3, c8 = (c & 7) * 8;
-            *(f16x8 *)(Ks + j * LD + c8) = *(const f16x8 *)(kg_ + (size_t)j * a.d + c8);
+            *(f16x8 *)(Ks + j * LD + c8) = *(const f16x8 *)(kg_ + swx_kidx(kl, j, h, c & 7));
             *(f16x8 *)(Vs + j * LD + c8) = *(const f16x8 *)(vg_ + (size_t)j * a.d + c8);
         }
     }
@@ -1203,9 +1219,10 @@ __global__ __launch_bounds__(64 * NQW) void self_attn_cached_mq_f16(SelfAttnArgs
 // position 111 for 100 rows of large-v3: at the end of a window's decode this kernel is bandwidth-, not latency-bound).
 // WPB (round 6 experiment, SWX_FLAG_SELFATTN_WG5): waves per workgroup -- WPB consecutive rows of one head (the beams of a window)
 // share a workgroup, i.e. a CU's L1 and one workgroup dispatch; every wave still does exactly its row's arithmetic.
-template <bool LONG, int WPB = 1>
+template <bool LONG, int WPB = 1, bool CH = false>
 __global__ __launch_bounds__(64 * WPB) void self_attn_step_f16(SelfAttnArgs a)
 {
+    const KLayout kl = k_layout_of<CH>(a.kl, a.d);
     constexpr int PF = 16;                   // prefetched V fragments per lane (keys kg + 8 i, i < PF  <=>  j < 128)
     __shared__ float qs_all[WPB][DH];
     __shared__ float ps_all[WPB][512];
@@ -1229,13 +1246,13 @@ __global__ __launch_bounds__(64 * WPB) void self_attn_step_f16(SelfAttnArgs a)
     // ---- K rows of positions lane, lane + 64 and the V fragments of positions < 128: one batch of loads
     f16x8 k0[8], k1[8];
     {
-        const f16 *kr0 = kc + ((size_t)(has0 ? pr0 : r) * a.n_ctx + (has0 ? j0 : 0)) * d + h * DH;   // clamped, never predicated
+        const f16 *kr0 = k_key_ptr<CH>(kc, a.n_ctx, a.d, kl, has0 ? pr0 : r, has0 ? j0 : 0, h);   // clamped, never predicated
 #pragma unroll
-        for (int e = 0; e < 8; ++e) k0[e] = *(const f16x8 *)(kr0 + 8 * e);
+        for (int e = 0; e < 8; ++e) k0[e] = *(const f16x8 *)(kr0 + e * kl.sc);
         if (pos >= 64) {
-            const f16 *kr1 = kc + ((size_t)(has1 ? pr1 : r) * a.n_ctx + (has1 ? j1 : 0)) * d + h * DH;
+            const f16 *kr1 = k_key_ptr<CH>(kc, a.n_ctx, a.d, kl, has1 ? pr1 : r, has1 ? j1 : 0, h);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) k1[e] = *(const f16x8 *)(kr1 + 8 * e);
+            for (int e = 0; e < 8; ++e) k1[e] = *(const f16x8 *)(kr1 + e * kl.sc);
         }
     }
     const int kg = lane >> 3, dc = (lane & 7) * 8;
@@ -1294,9 +1311,9 @@ __global__ __launch_bounds__(64 * WPB) void self_attn_step_f16(SelfAttnArgs a)
                     if (128 + 64 * c <= pos) {              // uniform: the chunk holds a cached position
                         const int j = lane + 128 + 64 * c;
                         const bool has = j <= pos;
-                        const f16 *kr = kc + ((size_t)(has ? prt[c] : r) * a.n_ctx + (has ? j : 0)) * d + h * DH;
+                        const f16 *kr = k_key_ptr<CH>(kc, a.n_ctx, a.d, kl, has ? prt[c] : r, has ? j : 0, h);
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) kt[u][e] = *(const f16x8 *)(kr + 8 * e);
+                        for (int e = 0; e < 8; ++e) kt[u][e] = *(const f16x8 *)(kr + e * kl.sc);
                     }
                 }
 #pragma unroll
@@ -1384,8 +1401,10 @@ __global__ __launch_bounds__(64 * WPB) void self_attn_step_f16(SelfAttnArgs a)
 // = pos0 + two round trips.  Per score and per output element the expressions and their ORDER are self_attn_step_f16's (one lane owns
 // a key's whole dot product; a lane group accumulates its keys in ascending order), so the result is bit-identical
 // (tests/hw_checks/self_attn_check.py, tests/test_gpu_model.py).  Dispatched for R x H <= 1024 (SWX_FLAG_SELFATTN_NO_DEEP: A/B).
+template <bool CH = false>
 __global__ __launch_bounds__(64) void self_attn_step_long_f16(SelfAttnArgs a)
 {
+    const KLayout kl = k_layout_of<CH>(a.kl, a.d);
     constexpr int PF = 16;                   // V fragments per lane of positions < 128 (keys kg + 8 i)
     constexpr int NC = 5;                    // 64-position chunks past 128: 128 + 64 * 5 = 448 = n_text_ctx
     __shared__ float qs[DH];
@@ -1410,9 +1429,9 @@ __global__ __launch_bounds__(64) void self_attn_step_long_f16(SelfAttnArgs a)
     auto load_k = [&](int c, f16x8 (&kk)[8]) {
         const int j = lane + 64 * c;
         const bool has = j <= pos;
-        const f16 *kr = kc + ((size_t)(has ? pr[c] : r) * a.n_ctx + (has ? j : 0)) * d + h * DH;     // clamped, never predicated
+        const f16 *kr = k_key_ptr<CH>(kc, a.n_ctx, a.d, kl, has ? pr[c] : r, has ? j : 0, h);     // clamped, never predicated
 #pragma unroll
-        for (int e = 0; e < 8; ++e) kk[e] = *(const f16x8 *)(kr + 8 * e);
+        for (int e = 0; e < 8; ++e) kk[e] = *(const f16x8 *)(kr + e * kl.sc);
     };
     // the V side's ancestor ids (lane group kg reads keys kg + 8 u of every chunk: the id sits in lane kg + 8 u): all 56 exchanges as ONE
     // batch in front of the loads -- inside the guarded load blocks each exchange is an LDS round trip of its own in front of its load
@@ -1796,9 +1815,12 @@ int swx_self_attn_plan(int dtype, const SelfAttnArgs &a, int row_mul, int flags)
     return SWX_SA_K_CACHED_F16;
 }
 
-int swx_self_attention(int dtype, const SelfAttnArgs &a, int row_mul, hipStream_t s)
+int swx_self_attention(int dtype, const SelfAttnArgs &a_in, int row_mul, hipStream_t s)
 {
-    if (a.R <= 0 || a.n_new <= 0) return 0;
+    if (a_in.R <= 0 || a_in.n_new <= 0) return 0;
+    SelfAttnArgs a = a_in;
+    if (!a.kl.sp) a.kl = swx_klayout(0, a.n_ctx, a.d);
+    if (dtype != SWX_F16 && a.kl.sp != a.d) return -5;      // the chunked K cache is the f16 engine's
     const int kid = swx_self_attn_plan(dtype, a, row_mul, swx_flags());
     if (kid < 0) return kid;
     // algorithmic bytes: K and V of every cached position of every row once (+ q in, o out); the positions are device state --
@@ -1807,48 +1829,46 @@ int swx_self_attention(int dtype, const SelfAttnArgs &a, int row_mul, hipStream_
     SwxProfScope prof(PC_SELF_ATTN, (double)a.R * a.n_new * a.d * (dtype == SWX_F16 ? 2 : 4) * (2.0 * npos + 2.0), s);
     dim3 g1(a.n_new, a.R);
     dim3 g2(a.n_new, a.H, a.R);
+    const bool ch = a.kl.sp != a.d;           // chunked K cache rows: the CH instantiation of the reader
+    auto launch_mq = [&](auto kern, int nqw) -> int {
+        const int lds_rows = ((a.n_new + 7) / 8) * 8;
+        const size_t lds = (size_t)lds_rows * 72 * 2 * 2 + (size_t)nqw * 64 * 4 + (size_t)nqw * lds_rows * 4;
+        static bool attr = false;             // (one per instantiation of this lambda = per kernel)
+        if (!attr) {
+            hipError_t e_ = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
+            if (e_ != hipSuccess) return -100 - (int)e_;
+            attr = true;
+        }
+        hipLaunchKernelGGL(kern, dim3(cdiv(a.n_new, nqw), a.H, a.R), dim3(64 * nqw), lds, s, a, row_mul, lds_rows);
+        return 0;
+    };
+#define SWX_SA_LAUNCH(K0, K1, grid, block, ...) \
+    do { if (ch) hipLaunchKernelGGL((K1), grid, block, 0, s, __VA_ARGS__); else hipLaunchKernelGGL((K0), grid, block, 0, s, __VA_ARGS__); } while (0)
     switch (kid) {
-        case SWX_SA_K_STEP_WG5: hipLaunchKernelGGL((self_attn_step_f16<false, 5>), dim3(a.H, cdiv(a.R, 5)), dim3(320), 0, s, a); break;
-        case SWX_SA_K_STEP: hipLaunchKernelGGL((self_attn_step_f16<false, 1>), dim3(a.H, a.R), dim3(64), 0, s, a); break;
-        case SWX_SA_K_STEP_DEEP: hipLaunchKernelGGL(self_attn_step_long_f16, dim3(a.H, a.R), dim3(64), 0, s, a); break;
-        case SWX_SA_K_STEP_LONG_WG5: hipLaunchKernelGGL((self_attn_step_f16<true, 5>), dim3(a.H, cdiv(a.R, 5)), dim3(320), 0, s, a); break;
-        case SWX_SA_K_STEP_LONG: hipLaunchKernelGGL((self_attn_step_f16<true, 1>), dim3(a.H, a.R), dim3(64), 0, s, a); break;
+        case SWX_SA_K_STEP_WG5: SWX_SA_LAUNCH((self_attn_step_f16<false, 5, false>), (self_attn_step_f16<false, 5, true>), dim3(a.H, cdiv(a.R, 5)), dim3(320), a); break;
+        case SWX_SA_K_STEP: SWX_SA_LAUNCH((self_attn_step_f16<false, 1, false>), (self_attn_step_f16<false, 1, true>), dim3(a.H, a.R), dim3(64), a); break;
+        case SWX_SA_K_STEP_DEEP: SWX_SA_LAUNCH((self_attn_step_long_f16<false>), (self_attn_step_long_f16<true>), dim3(a.H, a.R), dim3(64), a); break;
+        case SWX_SA_K_STEP_LONG_WG5: SWX_SA_LAUNCH((self_attn_step_f16<true, 5, false>), (self_attn_step_f16<true, 5, true>), dim3(a.H, cdiv(a.R, 5)), dim3(320), a); break;
+        case SWX_SA_K_STEP_LONG: SWX_SA_LAUNCH((self_attn_step_f16<true, 1, false>), (self_attn_step_f16<true, 1, true>), dim3(a.H, a.R), dim3(64), a); break;
         case SWX_SA_K_MQ4:
         case SWX_SA_K_MQ8: {
             if (!a.skip_append) hipLaunchKernelGGL(kv_append_kernel<f16>, g1, dim3(256), 0, s, a, row_mul);
-            const int nqw = kid == SWX_SA_K_MQ8 ? 8 : 4;
-            const int lds_rows = ((a.n_new + 7) / 8) * 8;
-            const size_t lds = (size_t)lds_rows * 72 * 2 * 2 + (size_t)nqw * 64 * 4 + (size_t)nqw * lds_rows * 4;
-            dim3 gq(cdiv(a.n_new, nqw), a.H, a.R);
-            if (nqw == 8) {
-                static bool attr8 = false;
-                if (!attr8) {
-                    hipError_t e_ = hipFuncSetAttribute((const void *)self_attn_cached_mq_f16<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-                    if (e_ != hipSuccess) return -100 - (int)e_;
-                    attr8 = true;
-                }
-                hipLaunchKernelGGL(self_attn_cached_mq_f16<8>, gq, dim3(512), lds, s, a, row_mul, lds_rows);
-            } else {
-                static bool attr4 = false;
-                if (!attr4) {
-                    hipError_t e_ = hipFuncSetAttribute((const void *)self_attn_cached_mq_f16<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-                    if (e_ != hipSuccess) return -100 - (int)e_;
-                    attr4 = true;
-                }
-                hipLaunchKernelGGL(self_attn_cached_mq_f16<4>, gq, dim3(256), lds, s, a, row_mul, lds_rows);
-            }
+            const int rc = kid == SWX_SA_K_MQ8 ? (ch ? launch_mq(self_attn_cached_mq_f16<8, true>, 8) : launch_mq(self_attn_cached_mq_f16<8, false>, 8))
+                                               : (ch ? launch_mq(self_attn_cached_mq_f16<4, true>, 4) : launch_mq(self_attn_cached_mq_f16<4, false>, 4));
+            if (rc < 0) return rc;
             break;
         }
         case SWX_SA_K_CACHED_F16:
             if (!a.skip_append) hipLaunchKernelGGL(kv_append_kernel<f16>, g1, dim3(256), 0, s, a, row_mul);
-            hipLaunchKernelGGL(self_attn_cached<f16>, g2, dim3(64), 0, s, a, row_mul);
+            SWX_SA_LAUNCH((self_attn_cached<f16, false>), (self_attn_cached<f16, true>), g2, dim3(64), a, row_mul);
             break;
         case SWX_SA_K_CACHED_F32:
             if (!a.skip_append) hipLaunchKernelGGL(kv_append_kernel<float>, g1, dim3(256), 0, s, a, row_mul);
-            hipLaunchKernelGGL(self_attn_cached<float>, g2, dim3(64), 0, s, a, row_mul);
+            hipLaunchKernelGGL((self_attn_cached<float, false>), g2, dim3(64), 0, s, a, row_mul);
             break;
         default: return -5;
     }
+#undef SWX_SA_LAUNCH
     SWX_CHECK_LAUNCH();
     return 0;
 }

@@ -332,8 +332,10 @@ __global__ __launch_bounds__(64 * WPB) void gemm_dec_f16(DecGemmArgs g)
         } else if (E_QKV && n >= g.d) {
             const int rps = g.rps > 1 ? g.rps : 1;
             const int seq = m / rps, crow = seq * (g.row_mul > 1 ? g.row_mul : 1), pos = g.pos0[crow] + (m - seq * rps);
-            f16 *cache = n < 2 * g.d ? g.kcache : g.vcache;
-            dst = cache + ((size_t)crow * g.n_ctx + pos) * g.d + (n < 2 * g.d ? n - g.d : n - 2 * g.d);
+            // (columns n .. n + 3 lie inside one 8-dim chunk of a head: one 8-byte store in either K layout)
+            const int ck = n - g.d, cv = n - 2 * g.d;
+            dst = n < 2 * g.d ? g.kcache + (size_t)crow * g.n_ctx * g.d + swx_kidx(g.kl, pos, ck >> 6, (ck >> 3) & 7) + (ck & 7)
+                              : g.vcache + ((size_t)crow * g.n_ctx + pos) * g.d + cv;
         } else {
             dst = g.C + (size_t)m * g.ldc + n;
         }
@@ -523,8 +525,10 @@ __global__ __launch_bounds__(64 * WPB) void gemm_dectall_f16(DecGemmArgs g)
             for (int e = 0; e < 4; ++e) v[e] += (float)xres[e];
         } else if (E_QKV && n >= g.d) {
             const int seq = m / rps, crow = seq * (g.row_mul > 1 ? g.row_mul : 1), pos = posv + (m - seq * rps);
-            f16 *cache = n < 2 * g.d ? g.kcache : g.vcache;
-            dst = cache + ((size_t)crow * g.n_ctx + pos) * g.d + (n < 2 * g.d ? n - g.d : n - 2 * g.d);
+            // (columns n .. n + 3 lie inside one 8-dim chunk of a head: one 8-byte store in either K layout)
+            const int ck = n - g.d, cv = n - 2 * g.d;
+            dst = n < 2 * g.d ? g.kcache + (size_t)crow * g.n_ctx * g.d + swx_kidx(g.kl, pos, ck >> 6, (ck >> 3) & 7) + (ck & 7)
+                              : g.vcache + ((size_t)crow * g.n_ctx + pos) * g.d + cv;
         } else {
             dst = g.C + (size_t)m * g.ldc + n;
         }
@@ -655,6 +659,7 @@ int swx_dec_kernel_plan(int M, int N, int K, int epi_in, int tall, bool ticket_o
 int swx_gemm_dec(DecGemmArgs g, hipStream_t s)
 {
     if (g.M <= 0 || g.N <= 0) return 0;
+    if (!g.kl.sp) g.kl = swx_klayout(0, g.n_ctx, g.d);
     if (g.lda % 8 != 0 || ((uintptr_t)g.A & 15) || ((uintptr_t)g.W & 15)) return -4;      // g.W: packed (swx_fold_ln)
     int mt = 1, ks2 = 1;
     bool ticket = false;

@@ -83,9 +83,31 @@ int swx_gemm_plan_f16(int M, int N, int K, int epi, int64_t ldc, int64_t ldr, bo
 #define SWX_FLAG_XKV_PACK_SEPARATE 128     // cross-K/V: the fragment-ordered copy by its own launch (swx_xkv_pack, rounds 2-5) instead of by the projection's epilogue (A/B; the same bytes)
 #define SWX_FLAG_DEC_W1_FULL_TILE 256     // single-wave dec GEMM workgroups: DMA all 16 rows of the activation tile (rows past M clamped) instead of the rows that exist (A/B; bit-identical)
 #define SWX_FLAG_XQ_FULL_TILE 512          // decode cross-attention's fused query projection: DMA all 16 rows of the residual tile instead of the window's nq rows (A/B; bit-identical)
+#define SWX_FLAG_KCACHE_CHUNKED 2      // f16 decode: the self-attention K cache in position-contiguous 16-byte chunks per head (KLayout below) instead of
+                                      // row-major [n_ctx][d] like the V cache.  Bit-identical.  Measured: the step kernel 9.67 vs 9.75 us in the headline
+                                      // pass, whose passes it does not separate (407.5-408.5 vs 406.2-407.4 ms); sequential mode 4 600-4 610 vs
+                                      // 4 650-4 689 ms; stand-alone 15 % slower when neighbouring keys come from different beams, 14 % faster when
+                                      // from one row.  Off by default (profiles/kcache_layout_*)
 #define SWX_FLAG_NO_BIG_TILE 131072   // tiled GEMM: never the 256 x 256 kernel (A/B; results are bit-identical)
 #define SWX_DEFAULT_FLAGS 0
 int swx_flags();
+
+// ---- layout of a row of the decoder self-attention K cache.  A row is always n_ctx * d elements at row * n_ctx * d; what the
+//      descriptor says is where element (pos, h, dim) lies INSIDE it, as three element strides:
+//        row-major [n_ctx][d]        sp = d, sh = 64,         sc = 8          (the V cache, the f32 engine, the scoring-pass cache)
+//        chunked   [H][8][n_ctx][8]  sp = 8, sh = 64 * n_ctx, sc = 8 * n_ctx  (the f16 decode cache under SWX_FLAG_KCACHE_CHUNKED)
+//      The step kernels give lane j key j and fetch its head's 128 bytes as eight 16-byte loads: row-major, one wave-instruction
+//      touches 64 cache lines 2 d bytes apart; chunked, load e of lane j is base(row, h) + e * n_ctx * 16 + 16 j -- 1 024
+//      contiguous bytes per run of lanes that share an ancestor row.  Every reader and writer of the K cache computes its
+//      addresses with swx_kidx (the readers' row-major instantiations with its strides as compile-time constants); sp == 0 (a
+//      zero-initialised descriptor) means row-major and is filled in by the launchers.
+struct KLayout { int sp, sh, sc; };      // element strides: position, head, 8-dim chunk of a head
+__host__ __device__ inline KLayout swx_klayout(int chunked, int n_ctx, int d)
+{
+    return chunked ? KLayout{8, 64 * n_ctx, 8 * n_ctx} : KLayout{d, 64, 8};
+}
+// element offset inside a cache row of the first of the 8 dims of chunk `chunk` (dims 8 chunk .. 8 chunk + 7) of head h at `pos`
+__host__ __device__ inline int swx_kidx(const KLayout &L, int pos, int h, int chunk) { return h * L.sh + chunk * L.sc + pos * L.sp; }
 
 // ---- decode-step GEMM (swx_decstep.hip): M split over workgroups, K whole -> the kernel finishes its own outputs (no f32
 //      slabs, no finish launch), LayerNorm folded into the consumer (statistics from the staged tile)
@@ -119,6 +141,7 @@ struct DecGemmArgs {
     int *ticket;                         // K-split shapes of the decode-step kernel: SWX_DEC_TICKETS zeroed ints (self-resetting arrival
                                          // counters per (panel, row group)) -> the slab reduction runs inside the launch; null: dec_slab_finish
     _Float16 *kcache, *vcache; const int32_t *pos0; int n_ctx, d;
+    KLayout kl;                          // DEC_QKV: layout of a K cache row (zeros: row-major)
     int rps;                             // DEC_QKV: rows per sequence (0 / 1: one new token per row); row m = sequence m / rps, token m % rps
     int row_mul;                         // DEC_QKV: cache row (and pos0 index) of sequence q = q * row_mul (0 / 1: q itself; the prefill writes row w * G)
     int ks2, kslice, n_rg; int64_t slab_stride;   // filled by the launcher
@@ -220,6 +243,7 @@ struct SelfAttnArgs {
                                      // budget), or 0 = unknown.  <= 128: the kernel variant without the code for positions >= 128
     int pos0_all_zero;               // multi-token pass: the host knows that every row starts at position 0 (a.pos0 is the zeros array):
                                      // several tokens of a (row, head) per workgroup with K / V staged in LDS (self_attn_cached_mq_f16)
+    KLayout kl;                      // layout inside a K cache row (zeros: row-major); the V cache is always row-major
 };
 // logical row of grid index ri is ri * row_mul (prefill of beam groups computes one row per window)
 int swx_self_attention(int dtype, const SelfAttnArgs &a, int row_mul, hipStream_t s);

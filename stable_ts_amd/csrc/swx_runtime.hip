@@ -360,6 +360,7 @@ struct FwdCfg {
     unsigned char *kcache, *vcache;
     size_t layer_stride;   // bytes between layers in the cache (0 = single-layer scratch)
     int cache_rows;        // rows per layer in the cache
+    int k_chunked;         // f16: the K cache rows are [H][8][n_ctx][8] (KLayout, swx_kernels.h: the decode caches) instead of row-major
     int32_t *anc;
     const unsigned char *xkv;
     bool capture; int cap_row0, cap_rows, cap_ld_n;
@@ -407,12 +408,13 @@ int decoder_step_dec(swx_model *m, const FwdCfg &f, hipStream_t s)
         g.A = x; g.lda = d; g.W = m->A<f16>(w.wqkv_f); g.ldw = d; g.N = 3 * d; g.K = d; g.epi = DEC_LN | DEC_QKV;
         g.c1 = m->A<float>(w.qkv_c1); g.c2 = m->A<float>(w.qkv_c2); g.C = q; g.ldc = d;
         g.kcache = kc; g.vcache = vc; g.pos0 = f.pos0; g.n_ctx = D.n_text_ctx; g.d = d;
+        g.kl = swx_klayout(f.k_chunked, D.n_text_ctx, d);
         g.pf = pf_of(w.wo_p, d, d, DEC_RES);                 // used after the self-attention (<= 57 MB through the cache)
         SWX_TRY(swx_gemm_dec(g, s));
         SelfAttnArgs sa{};
         sa.qkv = q; sa.ldqkv = d; sa.kcache = kc; sa.vcache = vc; sa.anc = f.anc; sa.pos0 = f.pos0; sa.o = att; sa.ldo = d;
         sa.R = rows; sa.n_new = 1; sa.H = H; sa.n_ctx = D.n_text_ctx; sa.d = d; sa.skip_append = 1; sa.step_cached = 1;
-        sa.step_pos = f.step_pos; sa.pos_bound = f.pos_bound;
+        sa.step_pos = f.step_pos; sa.pos_bound = f.pos_bound; sa.kl = g.kl;
         SWX_TRY(swx_self_attention(m->dtype, sa, 1, s));
         // x += att Wo^T + bo
         g = DecGemmArgs{};
@@ -490,11 +492,12 @@ int decoder_forward_dec(swx_model *m, const FwdCfg &f, hipStream_t s)
         g.M = rows; g.tall = 1; g.A = x; g.lda = d; g.W = m->A<f16>(w.wqkv_f); g.ldw = d; g.N = 3 * d; g.K = d; g.epi = DEC_LN | DEC_QKV;
         g.c1 = m->A<float>(w.qkv_c1); g.c2 = m->A<float>(w.qkv_c2); g.C = q; g.ldc = d;
         g.kcache = kc; g.vcache = vc; g.pos0 = f.pos0; g.n_ctx = D.n_text_ctx; g.d = d; g.rps = f.n_new; g.row_mul = f.row_mul;
+        g.kl = swx_klayout(f.k_chunked, D.n_text_ctx, d);
         g.pf = pf_of(w.wo_p, d, d, DEC_RES);
         SWX_TRY(swx_gemm_dec(g, s));
         SelfAttnArgs sa{};
         sa.qkv = q; sa.ldqkv = d; sa.kcache = kc; sa.vcache = vc; sa.anc = f.anc; sa.pos0 = f.pos0; sa.o = att; sa.ldo = d;
-        sa.R = R; sa.n_new = f.n_new; sa.H = H; sa.n_ctx = D.n_text_ctx; sa.d = d; sa.skip_append = 1;
+        sa.R = R; sa.n_new = f.n_new; sa.H = H; sa.n_ctx = D.n_text_ctx; sa.d = d; sa.skip_append = 1; sa.kl = g.kl;
         sa.pos0_all_zero = f.pos0 == m->Wp<int32_t>(m->L.zeros_i32) ? 1 : 0;
         SWX_TRY(swx_self_attention(m->dtype, sa, f.row_mul, s));
         g = DecGemmArgs{};
@@ -577,6 +580,7 @@ int decoder_forward(swx_model *m, const FwdCfg &f, hipStream_t s)
         sa.vcache = f.vcache + (size_t)l * f.layer_stride;
         sa.anc = f.anc; sa.pos0 = f.pos0; sa.o = att; sa.ldo = d;
         sa.R = R; sa.n_new = f.n_new; sa.H = H; sa.n_ctx = D.n_text_ctx; sa.d = d;
+        sa.kl = swx_klayout(f.k_chunked, D.n_text_ctx, d);
         sa.pos0_all_zero = f.pos0 == m->Wp<int32_t>(m->L.zeros_i32) ? 1 : 0;
         SWX_TRY(swx_self_attention(m->dtype, sa, f.row_mul, s));
         SWX_TRY(gemm_residual(m, att, d, w.wo, w.bo, x, d, rows, d, d, s));
@@ -620,9 +624,9 @@ int logits_gemm(swx_model *m, const void *hid, int64_t ld, int rows, float *out,
 
 // The captured two-step graph of a decode job, from the handle's cache or captured now.  `record` enqueues the two units on the
 // stream it is given.  The key lists everything a kernel argument of the step depends on: the decode configuration, the
-// buffers (workspace / arena / cross-K/V / timestamp mask), the switches.  Buffer CONTENTS are read at run time.
+// buffers (workspace / arena / cross-K/V / timestamp mask), the switches, the K cache layout the job latched.  Buffer CONTENTS are read at run time.
 template <typename F>
-swx_model::StepGraph *step_graph(swx_model *m, const DecodeBufs &b, const void *d_xkv, int cur, F record)
+swx_model::StepGraph *step_graph(swx_model *m, const DecodeBufs &b, const void *d_xkv, int cur, int k_chunked, F record)
 {
     const swx_decode_cfg &c = b.cfg;
     uint32_t tbits, pbits;
@@ -634,7 +638,7 @@ swx_model::StepGraph *step_graph(swx_model *m, const DecodeBufs &b, const void *
         (uint64_t)(int64_t)c.blank_token, (uint64_t)c.n_suppress, (uint64_t)c.min_tokens, (uint64_t)c.seed,
         (uint64_t)(uintptr_t)b.ts_mask, (uint64_t)(uintptr_t)b.win_uid, (uint64_t)(uintptr_t)d_xkv, (uint64_t)(uintptr_t)m->arena,
         (uint64_t)(uintptr_t)m->ws, (uint64_t)m->ws_bytes, (uint64_t)g_debug_flags, (uint64_t)cur, (uint64_t)m->is_folded(),
-        (uint64_t)(uintptr_t)c.noise, (uint64_t)(uintptr_t)b.begin};
+        (uint64_t)(uintptr_t)c.noise, (uint64_t)(uintptr_t)b.begin, (uint64_t)k_chunked};
     ++m->graph_clock;
     for (auto &g : m->graphs) if (g.key == key) { g.used = m->graph_clock; return &g; }
     if (!m->cap_stream && hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking) != hipSuccess) { m->cap_stream = nullptr; return nullptr; }
@@ -1516,6 +1520,9 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
     SWX_TRY(swx_decode_init(b, d_init_tokens, s));
 
     const size_t layer_stride = (size_t)m->max_rows * D.n_text_ctx * d * e;
+    // K cache layout of this job (KLayout, swx_kernels.h), latched HERE: the prefill writes the cache, every step reads and extends it
+    // and the captured step graph bakes the strides into its kernel arguments, so a switch flipped mid-job must not reach any of them
+    const int k_chunked = m->dtype == SWX_F16 && (g_debug_flags & SWX_FLAG_KCACHE_CHUNKED) ? 1 : 0;
     if (g_debug_flags & SWX_FLAG_TICKET) {
         // the in-launch slab reduction relies on arrival counters that every launch leaves at zero; a launch that was aborted (fault,
         // reset) would leave them non-zero and every later job would silently pick the wrong last arriver: 16 KB, once per job
@@ -1528,6 +1535,7 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
     f.tokens = b.tokens[0]; f.ld_tok = (int64_t)G * b.TS;
     f.pos0 = m->Wp<int32_t>(m->L.zeros_i32);      // all zeros (any stride)
     f.kcache = m->ws + m->L.kcache; f.vcache = m->ws + m->L.vcache; f.layer_stride = layer_stride; f.cache_rows = m->max_rows;
+    f.k_chunked = k_chunked;
     f.anc = nullptr; f.xkv = (const unsigned char *)d_xkv; f.capture = false;
     unsigned char *x = m->ws + m->L.x, *hid2 = m->ws + m->L.hid2;
     // the prefill logits live at the tail of the logits region so that replication to rows [0, M) never overlaps
@@ -1569,6 +1577,7 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
         g.W = W; g.rpw = G; g.row_mul = 1; g.n_new = 1;
         g.tokens = b.tokens[cur_in]; g.ld_tok = b.TS; g.pos0 = b.pos0;
         g.kcache = f.kcache; g.vcache = f.vcache; g.layer_stride = layer_stride; g.cache_rows = m->max_rows;
+        g.k_chunked = k_chunked;
         g.anc = use_anc ? b.anc[cur_in] : nullptr; g.xkv = (const unsigned char *)d_xkv; g.capture = false;
         // profiler's byte count only (steps = tokens sampled so far).  Never a captured kernel argument: a replayed graph would
         // carry the position of the step it was captured at (the profiler is off under replay, and 0 = "unknown" there)
@@ -1605,7 +1614,7 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
     for (int i = 1; !stop; ) {
         const bool pair = graph_ok && !m->graphs_off && !graph_failed_now && i >= 2 && (i & 1) == 0 && i + 1 < cfg->sample_len && n_min + i + 1 <= D.n_text_ctx;
         if (pair) {
-            if (!sg) sg = step_graph(m, b, d_xkv, cur, [&](hipStream_t cs) -> int {
+            if (!sg) sg = step_graph(m, b, d_xkv, cur, k_chunked, [&](hipStream_t cs) -> int {
                 SWX_TRY(unit(cur, cs, true));
                 return unit(cfg->beam ? cur ^ 1 : cur, cs, true);
             });
@@ -2036,6 +2045,15 @@ int swx_test_dec_gemm(const void *d_a, int64_t lda, const void *d_w, const float
                       void *d_c, int64_t ldc, void *d_x, void *d_kcache, void *d_vcache, const int32_t *d_pos0, int n_ctx, int d,
                       int M, int N, int K, int epilogue, void *d_scratch, size_t scratch_bytes, void *stream)
 {
+    return swx_test_dec_gemm_kl(d_a, lda, d_w, d_gamma, d_beta, d_bias, d_c, ldc, d_x, d_kcache, d_vcache, d_pos0, n_ctx, d, M, N, K, epilogue,
+                                0, 0, d_scratch, scratch_bytes, stream);
+}
+
+int swx_test_dec_gemm_kl(const void *d_a, int64_t lda, const void *d_w, const float *d_gamma, const float *d_beta, const float *d_bias,
+                         void *d_c, int64_t ldc, void *d_x, void *d_kcache, void *d_vcache, const int32_t *d_pos0, int n_ctx, int d,
+                         int M, int N, int K, int epilogue, int rps, int k_chunked, void *d_scratch, size_t scratch_bytes, void *stream)
+{
+    if (k_chunked && (epilogue & DEC_QKV) && (n_ctx <= 0 || d <= 0 || d % 64)) return -2;
     // d_scratch: N*K halfs (folded weights) + 2N floats (c1, c2) + the slab floats of the shape, 256-byte aligned pieces
     hipStream_t s = S(stream);
     unsigned char *p = (unsigned char *)d_scratch;
@@ -2057,6 +2075,8 @@ int swx_test_dec_gemm(const void *d_a, int64_t lda, const void *d_w, const float
     g.epi = epilogue & 31;
     g.tall = (epilogue & 64) ? 1 : 0;                 // bit 6: a multi-token pass (the tall kernel from 161 rows on)
     g.rps = (epilogue & 64) && (epilogue & DEC_QKV) ? 7 : 0;      // (QKV scatter of the tall test: 7 rows per sequence)
+    if (rps > 0 && (epilogue & DEC_QKV)) g.rps = rps;
+    g.kl = swx_klayout(k_chunked ? 1 : 0, n_ctx, d);
     if ((epilogue & DEC_LN) && (epilogue & 32)) {     // bit 5: d_w is already folded, d_gamma / d_beta are c1 / c2 (timing runs)
         g.W = (const f16 *)d_w; g.c1 = d_gamma; g.c2 = d_beta;
     } else if (epilogue & DEC_LN) {
@@ -2074,7 +2094,15 @@ int swx_test_dec_gemm(const void *d_a, int64_t lda, const void *d_w, const float
 int swx_test_self_attn_step(const void *d_q, void *d_kcache, void *d_vcache, const int32_t *d_anc, const int32_t *d_pos0,
                             int R, int H, int n_ctx, int d, int variant, void *d_o, void *stream)
 {
+    return swx_test_self_attn_step_kl(d_q, d_kcache, d_vcache, d_anc, d_pos0, R, H, n_ctx, d, variant, 0, d_o, stream);
+}
+
+int swx_test_self_attn_step_kl(const void *d_q, void *d_kcache, void *d_vcache, const int32_t *d_anc, const int32_t *d_pos0,
+                               int R, int H, int n_ctx, int d, int variant, int k_chunked, void *d_o, void *stream)
+{
+    if (d != 64 * H) return -2;
     SelfAttnArgs sa{};
+    sa.kl = swx_klayout(k_chunked ? 1 : 0, n_ctx, d);
     sa.qkv = d_q; sa.ldqkv = d; sa.kcache = d_kcache; sa.vcache = d_vcache; sa.anc = (int32_t *)d_anc; sa.pos0 = d_pos0;
     sa.o = d_o; sa.ldo = d; sa.R = R; sa.n_new = 1; sa.H = H; sa.n_ctx = n_ctx; sa.d = d; sa.skip_append = 1;
     sa.step_cached = variant < 2 ? 1 : 0;
@@ -2084,6 +2112,12 @@ int swx_test_self_attn_step(const void *d_q, void *d_kcache, void *d_vcache, con
 
 int swx_test_self_attn_multi(const void *d_q, void *d_kcache, void *d_vcache, int R, int H, int n_new, int n_ctx, int d, int mq,
                              void *d_o, void *stream)
+{
+    return swx_test_self_attn_multi_kl(d_q, d_kcache, d_vcache, R, H, n_new, n_ctx, d, mq, 0, d_o, stream);
+}
+
+int swx_test_self_attn_multi_kl(const void *d_q, void *d_kcache, void *d_vcache, int R, int H, int n_new, int n_ctx, int d, int mq,
+                                int k_chunked, void *d_o, void *stream)
 {
     static int32_t *d_zeros = nullptr;           // every row starts at position 0
     static int zeros_n = 0;
@@ -2100,6 +2134,8 @@ int swx_test_self_attn_multi(const void *d_q, void *d_kcache, void *d_vcache, in
     sa.qkv = d_q; sa.ldqkv = d; sa.kcache = d_kcache; sa.vcache = d_vcache; sa.anc = nullptr; sa.pos0 = d_zeros;
     sa.o = d_o; sa.ldo = d; sa.R = R; sa.n_new = n_new; sa.H = H; sa.n_ctx = n_ctx; sa.d = d; sa.skip_append = 1;
     sa.pos0_all_zero = mq ? 1 : 0;
+    if (k_chunked && d != 64 * H) return -2;
+    sa.kl = swx_klayout(k_chunked ? 1 : 0, n_ctx, d);
     return swx_self_attention(SWX_F16, sa, 1, S(stream));
 }
 
@@ -2107,7 +2143,18 @@ int swx_test_self_attn_general(int dtype, const void *d_qkv, int64_t ldqkv, void
                                const int32_t *d_pos0, int R, int H, int n_new, int n_ctx, int d, int row_mul, int skip_append,
                                int pos0_all_zero, void *d_o, void *stream)
 {
+    return swx_test_self_attn_general_kl(dtype, d_qkv, ldqkv, d_kcache, d_vcache, d_anc, d_pos0, R, H, n_new, n_ctx, d, row_mul, skip_append,
+                                         pos0_all_zero, 0, 0, d_o, stream);
+}
+
+// step_variant: 0 = the multi-token kernels; 1 / 2 = n_new == 1 through the decode-step kernels with pos_bound 128 / unknown (the long-context
+// kernels: with R * H <= 1024 the one that requests every load in two batches)
+int swx_test_self_attn_general_kl(int dtype, const void *d_qkv, int64_t ldqkv, void *d_kcache, void *d_vcache, const int32_t *d_anc,
+                                  const int32_t *d_pos0, int R, int H, int n_new, int n_ctx, int d, int row_mul, int skip_append,
+                                  int pos0_all_zero, int step_variant, int k_chunked, void *d_o, void *stream)
+{
     if (dtype != SWX_F16 && dtype != SWX_F32) return -1;
+    if (k_chunked && dtype != SWX_F16) return -2;
     if (!d_qkv || !d_kcache || !d_vcache || !d_pos0 || !d_o) return -1;
     if (R <= 0 || H <= 0 || n_new <= 0 || n_ctx <= 0 || n_ctx > 512 || n_new > n_ctx || d != 64 * H || row_mul < 1) return -2;
     if (ldqkv < (skip_append ? d : 3 * d)) return -2;
@@ -2115,7 +2162,30 @@ int swx_test_self_attn_general(int dtype, const void *d_qkv, int64_t ldqkv, void
     sa.qkv = d_qkv; sa.ldqkv = ldqkv; sa.kcache = d_kcache; sa.vcache = d_vcache; sa.anc = (int32_t *)d_anc; sa.pos0 = d_pos0;
     sa.o = d_o; sa.ldo = d; sa.R = R; sa.n_new = n_new; sa.H = H; sa.n_ctx = n_ctx; sa.d = d; sa.skip_append = skip_append ? 1 : 0;
     sa.pos0_all_zero = pos0_all_zero ? 1 : 0;
+    if (step_variant) { sa.step_cached = 1; sa.pos_bound = step_variant == 1 ? 128 : 0; }
+    sa.kl = swx_klayout(k_chunked ? 1 : 0, n_ctx, d);
     return swx_self_attention(dtype, sa, row_mul, S(stream));
+}
+
+int swx_test_kcache_index(int k_chunked, int n_ctx, int d, int pos, int h, int chunk)
+{
+    if (n_ctx <= 0 || d <= 0 || d % 64 || pos < 0 || pos >= n_ctx || h < 0 || h >= d / 64 || chunk < 0 || chunk >= 8) return -1;
+    return swx_kidx(swx_klayout(k_chunked ? 1 : 0, n_ctx, d), pos, h, chunk);
+}
+
+int swx_test_kcache_relayout(const void *h_src, void *h_dst, int64_t rows, int n_ctx, int d, int elem_bytes, int to_chunked)
+{
+    if (!h_src || !h_dst || h_src == h_dst || rows < 0 || n_ctx <= 0 || d <= 0 || d % 64 || elem_bytes <= 0) return -1;
+    const KLayout rm = swx_klayout(0, n_ctx, d), ch = swx_klayout(1, n_ctx, d);
+    const KLayout &from = to_chunked ? rm : ch, &to = to_chunked ? ch : rm;
+    const size_t cb = (size_t)8 * elem_bytes, row_b = (size_t)n_ctx * d * elem_bytes;
+    for (int64_t r = 0; r < rows; ++r)
+        for (int pos = 0; pos < n_ctx; ++pos)
+            for (int h = 0; h < d / 64; ++h)
+                for (int c = 0; c < 8; ++c)
+                    memcpy((unsigned char *)h_dst + r * row_b + (size_t)swx_kidx(to, pos, h, c) * elem_bytes,
+                           (const unsigned char *)h_src + r * row_b + (size_t)swx_kidx(from, pos, h, c) * elem_bytes, cb);
+    return 0;
 }
 
 int swx_test_self_attn_plan(int dtype, int R, int H, int n_new, int n_ctx, int row_mul, int skip_append, int step_cached, int pos_bound,
