@@ -216,6 +216,37 @@ int swx_heads_new(swx_model *m, const void *d_q, int max_n, int n_tok, int row0,
                   float *d_neg_matrix, int ld_f, void *d_scratch, size_t scratch_bytes, void *stream);
 int swx_weighted_sum(const float *const *h_xs, const float *h_coef, int n_in, float *d_out, int64_t n, void *stream);
 
+/* ---- the same stage for W windows of one batch in one call each (the kernels carry a window axis; a window's numbers are the
+ * bits the single-window calls above give it).  Token counts h_n_tok[w] <= max_n and frame counts h_n_frames[w] (clamped to
+ * [1, n_audio_ctx] inside) are ragged; the text-token rows of window w are n_sot .. n_tok[w] - 2 (max_rows = max_n - n_sot - 1).
+ *
+ * Cross-K/V: read IN PLACE from a batch buffer of xkv_W windows ([L][xkv_W][chunk], swx_cross_kv): d_xkv points at the chunk
+ *   of the FIRST of the W windows in layer 0; layer stride = xkv_W chunks, window stride = one chunk.  xkv_W = 0 means W.
+ * swx_score_q_batch: d_tokens int32 [W][max_n] (rows padded with eot), d_q receives [n_text_layer][W][max_n][d] in the compute
+ *   dtype (swx_qcap_batch_bytes), d_token_probs f32 [W][max_n] or NULL.  Refuses (-1) a window with n_tok - n_sot - 2 < 0.
+ *   Needs a workspace bound for >= W windows.
+ * swx_heads_dynamic_batch: score -> pick -> gather -> z-normalisation / median / head mean (swx_align_weights' kernels) in one
+ *   call; d_peaks f64 [W][max_rows] (the previous DTW pass's jump midpoints) or NULL (every row's own peak); d_neg_matrix f32
+ *   [W][max_rows][ld_f] (ld_f = n_audio_ctx) receives the NEGATED matrix: rows < n_tok[w] - n_sot - 1 and frames < n_frames[w]
+ *   of window w are written, nothing else.
+ * swx_heads_new_batch: the same output layout for aligner = 'new' (options as swx_heads_new).
+ * d_scratch: swx_heads_batch_scratch_bytes(m, W, max_n, count) of device memory (count = 0 for swx_heads_new_batch): the
+ *   per-window counts, head scores and picks, column norms, and for count > 0 the gathered scores [W][count][max_rows][n_audio_ctx]
+ *   with their row statistics.  Nothing is allocated inside.
+ * Errors: -1 null / out-of-range arguments, -2 / -3 from the launchers (shape / median width), -8 short scratch or workspace. */
+size_t swx_qcap_batch_bytes(const swx_model *m, int W, int max_n);
+int swx_score_q_batch(swx_model *m, const int32_t *d_tokens, const int32_t *h_n_tok, int W, int max_n, int n_sot, int eot,
+                      const void *d_xkv, int xkv_W, float *d_token_probs, void *d_q, void *stream);
+size_t swx_heads_batch_scratch_bytes(const swx_model *m, int W, int max_n, int count);
+int swx_heads_dynamic_batch(swx_model *m, const void *d_q, int W, int max_n, int n_sot, const int32_t *h_n_tok,
+                            const int32_t *h_n_frames, const void *d_xkv, int xkv_W, float qk_scale, int medfilt_width, int count,
+                            const double *d_peaks, float *d_neg_matrix, int ld_f, void *d_scratch, size_t scratch_bytes,
+                            void *stream);
+int swx_heads_new_batch(swx_model *m, const void *d_q, int W, int max_n, int n_sot, const int32_t *h_n_tok,
+                        const int32_t *h_n_frames, const void *d_xkv, int xkv_W, float qk_scale, int medfilt_width, int topk,
+                        float w_colnorm, float w_rownorm, float w_coverage, float *d_neg_matrix, int ld_f, void *d_scratch,
+                        size_t scratch_bytes, void *stream);
+
 /* full-sequence logits of a teacher-forced pass (model(mel, tokens) as used by refine/locate; also a test hook):
  * d_logits f32 [W][max_n][n_vocab].  Language detection (model.detect_language, original_whisper.py:329) is this call
  * with tokens = [[sot]]. */

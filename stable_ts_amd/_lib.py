@@ -76,6 +76,14 @@ SYMBOLS = {
     "swx_heads_new": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_float, c_int, c_int, c_float,
                               c_float, c_float, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "swx_weighted_sum": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "swx_qcap_batch_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "swx_score_q_batch": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                                  c_void_p, c_void_p]),
+    "swx_heads_batch_scratch_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "swx_heads_dynamic_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_int,
+                                        c_float, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "swx_heads_new_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_int,
+                                    c_float, c_int, c_int, c_float, c_float, c_float, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "swx_forward_logits": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "swx_forward_token_ranks": (c_int, [c_void_p, c_void_p, POINTER(c_int32), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),

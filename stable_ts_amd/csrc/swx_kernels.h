@@ -284,6 +284,19 @@ int swx_headsel_new_launch(int dtype, const void *qcap, int max_n, int d, int n,
                            int64_t layer_stride, int L, int H, int F, float qk_scale, int medfilt_width, int topk, float w_col,
                            float w_row, float w_cov, float *d_colnorm, float *d_score, int32_t *d_top, float *d_out, int out_ld_f,
                            hipStream_t s);
+// the same kernels over a window axis: qcap [L][W][max_n][d], cross-K of (layer l, window w) at xkv + l * layer_stride +
+// w * win_stride (elements), per-window counts in device int32 [W] arrays (or null with W = 1 and the scalar next to it).
+// dynamic: d_score f64 [W][L*H][row_ld], d_sel [W][row_ld][count], d_peaks f64 [W][row_ld] or null, d_out [W][count][row_ld][out_ld_f].
+// new: d_colnorm [W][L*H][SWX_HS_MAXF], d_score / d_top [W][L*H], d_out [W][out_ld_n][out_ld_f] (negated mean).
+int swx_headsel_dynamic_batch_launch(int dtype, const void *qcap, int W, int max_n, int d, int row0, const int32_t *d_n_rows,
+                                     int n_rows1, int row_ld, const void *xkv, int64_t layer_stride, int64_t win_stride, int L, int H,
+                                     const int32_t *d_n_frames, int F1, int nk, float qk_scale, int count, const double *d_peaks,
+                                     double *d_score, int32_t *d_sel, float *d_out, int out_ld_f, hipStream_t s);
+int swx_headsel_new_batch_launch(int dtype, const void *qcap, int W, int max_n, int d, const int32_t *d_n_tok, int n1, int row0,
+                                 const int32_t *d_n_out, int n_out1, int max_out, const void *xkv, int64_t layer_stride,
+                                 int64_t win_stride, int L, int H, const int32_t *d_n_frames, int F1, float qk_scale, int medfilt_width,
+                                 int topk, float w_col, float w_row, float w_cov, float *d_colnorm, float *d_score, int32_t *d_top,
+                                 float *d_out, int out_ld_n, int out_ld_f, hipStream_t s);
 int swx_weighted_sum_launch(const float *const *h_xs, const float *h_coef, int n_in, float *d_out, int64_t n, hipStream_t s);
 
 // ---- swx_decode.hip

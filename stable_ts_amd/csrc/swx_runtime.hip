@@ -1650,7 +1650,7 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
 // ------------------------------------------------------------------------------------------------------ score
 // capture: raw qk of the alignment heads for token rows cap_row0 .. cap_row0 + cap_rows - 1 -> L.cap [W][n_align][cap_ld][1500]
 static int score_forward(swx_model *m, const int32_t *d_tokens, const int32_t *h_n_tok, int W, int max_n, int cap_row0,
-                         int cap_rows, int cap_ld, const void *d_xkv, bool capture, hipStream_t s, void *qcap = nullptr)
+                         int cap_rows, int cap_ld, const void *d_xkv, bool capture, hipStream_t s, void *qcap = nullptr, int xkv_W = 0)
 {
     const swx_dims &D = m->dims;
     if (W > m->max_windows) return -8;
@@ -1664,6 +1664,7 @@ static int score_forward(swx_model *m, const int32_t *d_tokens, const int32_t *h
     f.anc = nullptr; f.xkv = (const unsigned char *)d_xkv;
     f.capture = capture;
     f.qcap = (unsigned char *)qcap;
+    f.xkv_W = xkv_W;
     // A teacher-forced pass over several tokens: max_n is the longest window's count, and a window of <= 16 tokens must get the
     // numbers it gets next to a longer one (transcribe_many / transcribe_spans: windows of different recordings share the scoring
     // pass).  A single-token pass (max_n == 1) is one query per window in any batch and keeps the key-split kernel.
@@ -1981,6 +1982,129 @@ int swx_heads_new(swx_model *m, const void *d_q, int max_n, int n_tok, int row0,
     return swx_headsel_new_launch(m->dtype, d_q, max_n, D.n_text_state, n_tok, row0, n_out, d_xkv, xkv_chunk_elems(m), D.n_text_layer,
                                   D.n_text_head, F, qk_scale, medfilt_width, topk, w_colnorm, w_rownorm, w_coverage, colnorm, score, top,
                                   d_neg_matrix, ld_f, S(stream));
+}
+
+// ---- the same three calls for W windows of one batch.  The pass writes d_q [L][W][max_n][d]; the cross-K/V is read in place:
+// d_xkv points at the FIRST of the W windows inside a buffer of xkv_W windows (layer stride xkv_W * chunk, window stride chunk;
+// xkv_W = 0 means W), so a sub-batch of a larger job is an offset, not a copy.
+size_t swx_qcap_batch_bytes(const swx_model *m, int W, int max_n)
+{
+    if (!m || W <= 0 || max_n <= 0) return 0;
+    return (size_t)W * swx_qcap_bytes(m, max_n);
+}
+
+int swx_score_q_batch(swx_model *m, const int32_t *d_tokens, const int32_t *h_n_tok, int W, int max_n, int n_sot, int eot,
+                      const void *d_xkv, int xkv_W, float *d_token_probs, void *d_q, void *stream)
+{
+    if (!m || !m->arena || !m->ws) return -9;
+    if (!d_q || !d_tokens || !h_n_tok || !d_xkv || W < 0 || xkv_W < 0 || (xkv_W && xkv_W < W)) return -1;
+    if (W == 0) return 0;
+    for (int w = 0; w < W; ++w) if (h_n_tok[w] - n_sot - 2 < 0) return -1;
+    hipStream_t s = S(stream);
+    SWX_TRY(score_forward(m, d_tokens, h_n_tok, W, max_n, 0, 0, max_n, d_xkv, false, s, d_q, xkv_W));
+    if (d_token_probs) SWX_TRY(score_token_probs(m, d_tokens, W, max_n, n_sot, eot, d_token_probs, s));
+    return 0;
+}
+
+// scratch of the two batch calls: the per-window counts, then per window what swx_heads_scratch_bytes lists, then (count > 0) the
+// gathered raw scores [W][count][max_rows][n_audio_ctx] f32 and the row statistics swx_align_weights_launch needs
+struct HeadsBatchScratch { size_t cnt, score, sel, colnorm, nscore, top, gathered, rstat, total; };
+static HeadsBatchScratch heads_batch_layout(const swx_model *m, int W, int max_n, int count)
+{
+    const size_t LH = (size_t)m->dims.n_text_layer * m->dims.n_text_head, w = (size_t)W, c = count > 0 ? (size_t)count : 0;
+    HeadsBatchScratch L{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += align_up(bytes); return at; };
+    L.cnt = take(3 * w * sizeof(int32_t));
+    L.score = take(w * LH * max_n * sizeof(double));
+    L.sel = take(w * max_n * (c ? c : 1) * sizeof(int32_t));
+    L.colnorm = take(w * LH * SWX_HS_MAXF * sizeof(float));
+    L.nscore = take(w * LH * sizeof(float));
+    L.top = take(w * LH * sizeof(int32_t));
+    L.gathered = take(w * c * max_n * m->dims.n_audio_ctx * sizeof(float));
+    L.rstat = take(w * c * max_n * sizeof(float2));
+    L.total = off;
+    return L;
+}
+// validates the per-window counts and puts [n_tok | n_rows | n_frames (clamped to [1, n_audio_ctx])] at the head of the scratch
+static int heads_batch_counts(swx_model *m, int W, int max_n, int n_sot, const int32_t *h_n_tok, const int32_t *h_n_frames, int32_t *d_cnt,
+                       hipStream_t s)
+{
+    const swx_dims &D = m->dims;
+    std::vector<int32_t> hv(3 * (size_t)W);
+    for (int w = 0; w < W; ++w) {
+        if (h_n_tok[w] <= 0 || h_n_tok[w] > max_n || h_n_tok[w] - n_sot - 1 <= 0) return -1;
+        hv[w] = h_n_tok[w];
+        hv[W + w] = h_n_tok[w] - n_sot - 1;
+        const int F = h_n_frames[w];
+        hv[2 * W + w] = F < 1 ? 1 : (F > D.n_audio_ctx ? D.n_audio_ctx : F);
+    }
+    hipError_t er = hipMemcpyAsync(d_cnt, hv.data(), hv.size() * 4, hipMemcpyHostToDevice, s);
+    if (er == hipSuccess) er = hipStreamSynchronize(s);      // hv is a stack-lifetime staging buffer
+    return er == hipSuccess ? 0 : -100 - (int)er;
+}
+
+size_t swx_heads_batch_scratch_bytes(const swx_model *m, int W, int max_n, int count)
+{
+    if (!m || W <= 0 || max_n <= 0 || count < 0) return 0;
+    return heads_batch_layout(m, W, max_n, count).total;
+}
+
+// dynamic_heads for the text-token rows (n_sot .. n_tok[w] - 2) of every window: score -> pick -> gather -> the default path's
+// z-normalisation / median / head mean; d_neg_matrix f32 [W][max_n - n_sot - 1][ld_f] receives the NEGATED matrix (rows
+// < n_tok[w] - n_sot - 1, frames < n_frames[w]; nothing else is written).  d_peaks: null or f64 [W][max_n - n_sot - 1].
+int swx_heads_dynamic_batch(swx_model *m, const void *d_q, int W, int max_n, int n_sot, const int32_t *h_n_tok,
+                            const int32_t *h_n_frames, const void *d_xkv, int xkv_W, float qk_scale, int medfilt_width, int count,
+                            const double *d_peaks, float *d_neg_matrix, int ld_f, void *d_scratch, size_t scratch_bytes, void *stream)
+{
+    if (!m || !m->arena) return -9;
+    if (!d_q || !d_xkv || !d_neg_matrix || !d_scratch || !h_n_tok || !h_n_frames) return -1;
+    const swx_dims &D = m->dims;
+    if (W < 0 || xkv_W < 0 || (xkv_W && xkv_W < W) || n_sot < 0 || max_n - n_sot - 1 <= 0 || max_n > D.n_text_ctx || count <= 0 ||
+        ld_f != D.n_audio_ctx)
+        return -1;
+    if (W == 0) return 0;
+    const HeadsBatchScratch L = heads_batch_layout(m, W, max_n, count);
+    if (scratch_bytes < L.total) return -8;
+    hipStream_t s = S(stream);
+    unsigned char *p = (unsigned char *)d_scratch;
+    int32_t *cnt = (int32_t *)(p + L.cnt);
+    SWX_TRY(heads_batch_counts(m, W, max_n, n_sot, h_n_tok, h_n_frames, cnt, s));
+    const int max_rows = max_n - n_sot - 1;
+    const int64_t chunk = xkv_chunk_elems(m);
+    float *gathered = (float *)(p + L.gathered);
+    SWX_TRY(swx_headsel_dynamic_batch_launch(m->dtype, d_q, W, max_n, D.n_text_state, n_sot, cnt + W, 0, max_rows, d_xkv,
+                                             (int64_t)(xkv_W ? xkv_W : W) * chunk, chunk, D.n_text_layer, D.n_text_head, cnt + 2 * W, 0,
+                                             D.n_audio_ctx, qk_scale, count, d_peaks, (double *)(p + L.score), (int32_t *)(p + L.sel),
+                                             gathered, ld_f, s));
+    return swx_align_weights_launch(gathered, (float *)(p + L.rstat), nullptr, nullptr, W, count, max_rows, ld_f, cnt + W, cnt + 2 * W,
+                                    qk_scale, medfilt_width, d_neg_matrix, max_rows, ld_f, s);
+}
+
+// aligner = 'new' for every window over its own n_tok[w] rows; d_neg_matrix f32 [W][max_n - n_sot - 1][ld_f] as above
+int swx_heads_new_batch(swx_model *m, const void *d_q, int W, int max_n, int n_sot, const int32_t *h_n_tok, const int32_t *h_n_frames,
+                        const void *d_xkv, int xkv_W, float qk_scale, int medfilt_width, int topk, float w_colnorm, float w_rownorm,
+                        float w_coverage, float *d_neg_matrix, int ld_f, void *d_scratch, size_t scratch_bytes, void *stream)
+{
+    if (!m || !m->arena) return -9;
+    if (!d_q || !d_xkv || !d_neg_matrix || !d_scratch || !h_n_tok || !h_n_frames) return -1;
+    const swx_dims &D = m->dims;
+    if (W < 0 || xkv_W < 0 || (xkv_W && xkv_W < W) || n_sot < 0 || max_n - n_sot - 1 <= 0 || max_n > D.n_text_ctx ||
+        ld_f < D.n_audio_ctx)
+        return -1;
+    if (W == 0) return 0;
+    const HeadsBatchScratch L = heads_batch_layout(m, W, max_n, 0);
+    if (scratch_bytes < L.total) return -8;
+    hipStream_t s = S(stream);
+    unsigned char *p = (unsigned char *)d_scratch;
+    int32_t *cnt = (int32_t *)(p + L.cnt);
+    SWX_TRY(heads_batch_counts(m, W, max_n, n_sot, h_n_tok, h_n_frames, cnt, s));
+    const int max_out = max_n - n_sot - 1;
+    const int64_t chunk = xkv_chunk_elems(m);
+    return swx_headsel_new_batch_launch(m->dtype, d_q, W, max_n, D.n_text_state, cnt, 0, n_sot, cnt + W, 0, max_out, d_xkv,
+                                        (int64_t)(xkv_W ? xkv_W : W) * chunk, chunk, D.n_text_layer, D.n_text_head, cnt + 2 * W, 0,
+                                        qk_scale, medfilt_width, topk, w_colnorm, w_rownorm, w_coverage, (float *)(p + L.colnorm),
+                                        (float *)(p + L.nscore), (int32_t *)(p + L.top), d_neg_matrix, max_out, ld_f, s);
 }
 
 // d_out[e] = sum_j coef[j] * d_xs[j][e], n_in <= 8 (extra_models: the pooled matrix from each model's own head mean)

@@ -85,6 +85,8 @@ class Engine:
         self._next_token_suppress = (None, None)       # forward_next_token: (suppress list, its device copy)
         self.encode_calls = 0          # device passes through the encoder / 30-s windows in them (bench.py reports both)
         self.encode_windows = 0
+        self.score_q_calls = 0         # query-keeping scoring passes (score_q / score_q_batch) / windows in them
+        self.score_q_windows = 0
         self.reserve(max_windows, max_rows)
 
     def clone_shared(self, max_windows: Optional[int] = None, max_rows: Optional[int] = None) -> "Engine":
@@ -103,6 +105,7 @@ class Engine:
             e.set_alignment_heads(self._heads)
         e.max_windows, e.max_rows, e.ws = 0, 0, None
         e.encode_calls = e.encode_windows = 0
+        e.score_q_calls = e.score_q_windows = 0
         e._next_token_suppress = (None, None)
         e.reserve(self.max_windows if max_windows is None else max_windows, self.max_rows if max_rows is None else max_rows)
         return e
@@ -408,6 +411,8 @@ class Engine:
         check(self.lib.swx_score_q(self.h, _ptr(d_tok), _i32arr([n]), n, n_sot, eot, _ptr(xkv), _ptr(probs), _ptr(q), self.stream),
               "swx_score_q")
         scratch = torch.empty(self.lib.swx_heads_scratch_bytes(self.h, n), dtype=torch.uint8, device=self.device)
+        self.score_q_calls += 1
+        self.score_q_windows += 1
         p = probs.cpu().numpy()
         return dict(q=q, n=n, n_sot=n_sot, xkv=xkv, scratch=scratch, probs=p[0, :n - n_sot - 2].astype(np.float64).tolist())
 
@@ -442,6 +447,96 @@ class Engine:
         check(self.lib.swx_heads_new(self.h, _ptr(st["q"]), n, n, n_sot, rows, _ptr(st["xkv"]), int(n_frames), float(qk_scale),
                                      int(medfilt_width), int(topk), float(w_colnorm), float(w_rownorm), float(w_coverage),
                                      _ptr(neg), ld_f, _ptr(st["scratch"]), st["scratch"].numel(), self.stream), "swx_heads_new")
+        return neg
+
+    # ---- the same three calls for the W windows of a batch (swx_score_q_batch / swx_heads_*_batch): one library call each, the
+    #      cross-K/V read in place, nothing copied out but the token probabilities (once per pass)
+    def headsel_window_bytes(self, max_n: int, count: int = 0) -> int:
+        """Device bytes ONE window of ``max_n`` tokens adds to a batch state and its matrix: captured queries + scratch (with the
+        gathered scores of ``count`` dynamic heads) + the negated matrix.  timing.HEADSEL_BATCH_BYTES is divided by this."""
+        rows = max(int(max_n), 1)
+        return int(self.lib.swx_qcap_batch_bytes(self.h, 1, rows) + self.lib.swx_heads_batch_scratch_bytes(self.h, 1, rows, int(count))
+                   + rows * self.dims.n_audio_ctx * 4)
+
+    def score_q_batch(self, xkv: torch.Tensor, tokens_list: Sequence[Sequence[int]], *, n_sot: int, eot: int,
+                      window0: int = 0) -> dict:
+        """``score_q`` for W windows in ONE teacher-forced pass: ``tokens_list[k]`` belongs to window ``window0 + k`` of ``xkv``
+        (a sub-batch is an offset into the buffer, not a copy).  Keeps the queries as [L, W, max_n, d]; returns the batch state
+        ``heads_dynamic_batch`` / ``heads_new_batch`` take, with ``probs`` = one list of token probabilities per window."""
+        W = len(tokens_list)
+        n_tok = [len(t) for t in tokens_list]
+        max_n = max(n_tok)
+        xkv_W = int(xkv.n_windows)
+        assert 0 <= window0 and window0 + W <= xkv_W, (window0, W, xkv_W)
+        self.reserve(max(W, self.max_windows), max(self.max_rows, 1))
+        pad = np.full((W, max_n), eot, dtype=np.int32)
+        for w, t in enumerate(tokens_list):
+            pad[w, :len(t)] = t
+        d_tok = torch.tensor(pad, device=self.device)
+        probs = torch.zeros(W, max_n, dtype=torch.float32, device=self.device)
+        q = torch.empty(self.lib.swx_qcap_batch_bytes(self.h, W, max_n), dtype=torch.uint8, device=self.device)
+        chunk_bytes = self.lib.swx_cross_kv_bytes(self.h, 1) // self.dims.n_text_layer
+        xkv_ptr = ctypes.c_void_p(xkv.data_ptr() + window0 * chunk_bytes)
+        check(self.lib.swx_score_q_batch(self.h, _ptr(d_tok), _i32arr(n_tok), W, max_n, n_sot, eot, xkv_ptr, xkv_W, _ptr(probs),
+                                         _ptr(q), self.stream), "swx_score_q_batch")
+        self.score_q_calls += 1
+        self.score_q_windows += W
+        p = probs.cpu().numpy()
+        return dict(q=q, W=W, max_n=max_n, n_tok=n_tok, n_sot=n_sot, xkv=xkv, xkv_W=xkv_W, xkv_ptr=xkv_ptr, scratch=None,
+                    probs=[p[w, :n_tok[w] - n_sot - 2].astype(np.float64).tolist() for w in range(W)])
+
+    def _heads_batch_scratch(self, st: dict, count: int) -> torch.Tensor:
+        need = self.lib.swx_heads_batch_scratch_bytes(self.h, st["W"], st["max_n"], int(count))
+        if st["scratch"] is None or st["scratch"].numel() < need:
+            st["scratch"] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return st["scratch"]
+
+    def _heads_batch_out(self, st: dict, out: Optional[torch.Tensor]) -> torch.Tensor:
+        shape = (st["W"], st["max_n"] - st["n_sot"] - 1, self.dims.n_audio_ctx)
+        if out is None:
+            return torch.zeros(*shape, dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape, out.shape
+        return out
+
+    def heads_dynamic_batch(self, st: dict, n_frames_list: Sequence[int], *, count: int, qk_scale: float = 1.0, medfilt_width: int = 7,
+                            jump_indices_list=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``heads_dynamic`` for every window of a batch state in one call.  ``jump_indices_list``: None, or one array per window
+        (the previous DTW pass's jumps).  Returns the NEGATED matrices [W, max_rows, 1500] (f32, device): window w's block holds
+        its T_w + 1 rows and ``n_frames_list[w]`` frames; the rest keeps what ``out`` held (zeros when it is not given)."""
+        W, max_n, n_sot = st["W"], st["max_n"], st["n_sot"]
+        assert len(n_frames_list) == W
+        max_rows = max_n - n_sot - 1
+        peaks = None
+        if jump_indices_list is not None:                                # timing.py:96-98 per window, packed [W, max_rows]
+            assert len(jump_indices_list) == W
+            h_peaks = np.zeros((W, max_rows), dtype=np.float64)
+            for w, (jumps, F) in enumerate(zip(jump_indices_list, n_frames_list)):
+                j = np.pad(np.asarray(jumps), (0, 1), constant_values=int(F))
+                pk = np.ascontiguousarray(j[:-1] + ((j[1:] - j[:-1]) * 0.5), dtype=np.float64)
+                assert pk.size == st["n_tok"][w] - n_sot - 1
+                h_peaks[w, :pk.size] = pk
+            peaks = torch.from_numpy(h_peaks).to(self.device)
+        neg = self._heads_batch_out(st, out)
+        scratch = self._heads_batch_scratch(st, count)
+        check(self.lib.swx_heads_dynamic_batch(self.h, _ptr(st["q"]), W, max_n, n_sot, _i32arr(st["n_tok"]),
+                                               _i32arr([int(f) for f in n_frames_list]), st["xkv_ptr"], st["xkv_W"], float(qk_scale),
+                                               int(medfilt_width), int(count), _ptr(peaks), _ptr(neg), self.dims.n_audio_ctx,
+                                               _ptr(scratch), scratch.numel(), self.stream), "swx_heads_dynamic_batch")
+        return neg
+
+    def heads_new_batch(self, st: dict, n_frames_list: Sequence[int], *, qk_scale: float = 1.0, medfilt_width: int = 7, topk: int = 20,
+                        w_colnorm: float = 1, w_rownorm: float = 1, w_coverage: float = 0,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``heads_new`` for every window of a batch state in one call; the output as in ``heads_dynamic_batch``."""
+        W, max_n, n_sot = st["W"], st["max_n"], st["n_sot"]
+        assert len(n_frames_list) == W
+        neg = self._heads_batch_out(st, out)
+        scratch = self._heads_batch_scratch(st, 0)
+        check(self.lib.swx_heads_new_batch(self.h, _ptr(st["q"]), W, max_n, n_sot, _i32arr(st["n_tok"]),
+                                           _i32arr([int(f) for f in n_frames_list]), st["xkv_ptr"], st["xkv_W"], float(qk_scale),
+                                           int(medfilt_width), int(topk), float(w_colnorm), float(w_rownorm), float(w_coverage),
+                                           _ptr(neg), self.dims.n_audio_ctx, _ptr(scratch), scratch.numel(), self.stream),
+              "swx_heads_new_batch")
         return neg
 
     def pool_matrices(self, negs: Sequence[torch.Tensor], n_heads: Sequence[int]) -> torch.Tensor:

@@ -10,7 +10,9 @@ head-selection variants -- ``dynamic_heads`` (timing.py:87-103), ``aligner='new'
 ``extra_models`` (timing.py:177-189) -- are kernels too since round 3 (csrc/swx_headsel.hip): the pass keeps the
 cross-attention queries of every layer (``swx_score_q``, 8-37 MB) instead of every head's scores (0.4-1.7 GB in the
 reference), a head's score row is recomputed from q and the resident cross-K where it is needed; z-normalisation, median
-filter, head mean and DTW are the kernels of the default path.
+filter, head mean and DTW are the kernels of the default path.  All windows of a batched call go through them together
+(``swx_score_q_batch`` / ``swx_heads_dynamic_batch`` / ``swx_heads_new_batch``: one pass, one selection call and one DTW per
+refinement round), as they do on the default path.
 """
 import string
 from dataclasses import dataclass
@@ -169,16 +171,123 @@ def parse_dynamic_heads(dynamic_heads) -> tuple:
     return int(k), int(n)
 
 
-def _find_alignment_variants(model, jobs, xkv, *, medfilt_width, qk_scale, dynamic_heads, aligner, extra_models, mel,
-                             return_debug):
-    """timing.py:166-198 + 202-306 for the head-selection variants, one window at a time.  The per-head arithmetic runs in
-    csrc/swx_headsel.hip through the engine: ``score_q`` (the pass, keeping the cross-attention queries), ``heads_dynamic``
-    (timing.py:87-112), ``heads_new`` (timing.py:115-163), ``pool_matrices`` (timing.py:177-189); what stays here is the
-    control flow of the reference (which models, how many refinement iterations, which probabilities are averaged)."""
-    from .transcribe import _xkv_select
+# The head-selection variants take all windows of a job through the scoring pass, the head selection and the DTW together
+# (Engine.score_q_batch / heads_dynamic_batch / heads_new_batch).  False selects the per-window loop on the device engine too:
+# the parent code path, kept for A/B runs (scripts/bench_headsel_batch.py) and for the tests that compare the two.
+HEADSEL_BATCH = True
+# Device bytes the batch states of one sub-batch may hold (captured queries, selection scratch, gathered scores and matrices of
+# every model); a job whose windows need more is processed in consecutive sub-batches.  Engine.headsel_window_bytes gives the
+# per-window figure this is divided by ("Head selection over a window axis").
+HEADSEL_BATCH_BYTES = 2 << 30
+
+
+def _check_variant_args(model, aligner, extra_models):
     assert isinstance(aligner, dict) or aligner in ("new", "legacy"), f'aligner must be "new"/"legacy", got "{aligner}"'
     if extra_models and (bad := set(map(type, extra_models)) - {type(model)}):
         raise NotImplementedError(f"Got unsupported model type(s): {bad}")
+
+
+def _path_jumps(text_idx, time_idx):
+    jumps = np.pad(np.diff(text_idx), (1, 0), constant_values=1).astype(bool)
+    return time_idx[jumps].clip(min=0)
+
+
+def _find_alignment_variants(model, jobs, xkv, *, medfilt_width, qk_scale, dynamic_heads, aligner, extra_models, mel,
+                             return_debug):
+    """timing.py:166-198 + 202-306 for the head-selection variants.  The per-head arithmetic runs in csrc/swx_headsel.hip
+    through the engine; what stays here is the control flow of the reference (which models, how many refinement iterations,
+    which probabilities are averaged).  With an engine that has the batch calls (and ``HEADSEL_BATCH``) all windows advance
+    through the iterations together; otherwise (the CPU stand-in of the tests, or the switch off) one window at a time."""
+    eng = model.engine
+    if HEADSEL_BATCH and all(hasattr(eng, a) for a in ("score_q_batch", "heads_dynamic_batch", "heads_new_batch")):
+        return _find_alignment_variants_batch(model, jobs, xkv, medfilt_width=medfilt_width, qk_scale=qk_scale,
+                                              dynamic_heads=dynamic_heads, aligner=aligner, extra_models=extra_models, mel=mel)
+    return _find_alignment_variants_loop(model, jobs, xkv, medfilt_width=medfilt_width, qk_scale=qk_scale,
+                                         dynamic_heads=dynamic_heads, aligner=aligner, extra_models=extra_models, mel=mel)
+
+
+def _find_alignment_variants_batch(model, jobs, xkv, *, medfilt_width, qk_scale, dynamic_heads, aligner, extra_models, mel):
+    """All windows in lockstep: per refinement round ONE matrix call per model (``heads_dynamic_batch`` / ``heads_new_batch`` on a
+    batch state that is scored once, or the batched ``score`` without a head count), one ``pool_matrices`` call over the whole
+    [W, ...] block with ``extra_models``, one ``dtw`` call; the next round's jump indices are host arithmetic per window.  The
+    cross-K/V of a window is read where it lies in the batch buffer: no window is gathered out of it."""
+    _check_variant_args(model, aligner, extra_models)
+    tok = jobs[0].tokenizer
+    n_sot, eot = len(tok.sot_sequence), tok.eot
+    count, iterations = parse_dynamic_heads(dynamic_heads)
+    new = aligner != "legacy"
+    if not new and getattr(model, "missing_alignment_heads", False) and not count:
+        count = 6
+    extras = []
+    if extra_models and not new:
+        if mel is None:
+            raise ValueError("extra_models need the windows' log-mel (each model encodes the audio itself)")
+        extras = [(m, m.cross_kv(m.encoder(mel))) for m in extra_models]
+    new_options = {k: v for k, v in aligner.items()} if isinstance(aligner, dict) else {}
+    eng = model.engine
+    W = len(jobs)
+    # sub-batches: only the query-keeping passes hold per-window buffers (the batched `score` lives in the engine's workspace)
+    step = W
+    if new or count:
+        per_window = getattr(eng, "headsel_window_bytes", None)
+        if per_window is not None:
+            need = per_window(max(len(j.tokens) for j in jobs), 0 if new else count) * (1 + len(extras))
+            step = max(1, min(W, int(HEADSEL_BATCH_BYTES // max(need, 1))))
+    out = []
+    for w0 in range(0, W, step):
+        sub = jobs[w0:w0 + step]
+        toks, frames = [j.tokens for j in sub], [j.n_frames for j in sub]
+        n_rows = [len(t) - n_sot - 1 for t in toks]
+        states = {}
+
+        def state_of(m, xkv_m):
+            st = states.get(id(m))
+            if st is None:
+                st = states[id(m)] = m.engine.score_q_batch(xkv_m, toks, n_sot=n_sot, eot=eot, window0=w0)
+            return st
+
+        def legacy_matrix(m, xkv_m, jumps):
+            """one model's NEGATED head means [W, ld_n, 1500] + its token probabilities + how many heads went into them"""
+            if count:
+                st = state_of(m, xkv_m)
+                neg = m.engine.heads_dynamic_batch(st, frames, count=count, qk_scale=qk_scale, medfilt_width=medfilt_width,
+                                                   jump_indices_list=jumps)
+                return neg, st["probs"], count
+            assert w0 == 0 and len(sub) == W
+            p, neg, _ = m.engine.score(xkv_m, toks, frames, n_sot=n_sot, eot=eot, qk_scale=qk_scale, medfilt_width=medfilt_width)
+            return neg, p, m.engine.n_alignment_heads
+
+        jumps, probs, paths = None, [None] * len(sub), None
+        for _ in range(iterations or 1):
+            if new:
+                st = state_of(model, xkv)
+                neg = eng.heads_new_batch(st, frames, qk_scale=qk_scale, medfilt_width=medfilt_width, **new_options)
+                probs = list(st["probs"])
+            else:
+                neg, p, n_heads = legacy_matrix(model, xkv, jumps)
+                probs = [p[k] if probs[k] is None else probs[k] for k in range(len(sub))]   # the main model's pass is cached
+                if extras:
+                    negs, heads, extra_probs = [neg], [n_heads], []
+                    for m, xkv_m in extras:
+                        ne, pe, he = legacy_matrix(m, xkv_m, None)
+                        negs.append(ne)
+                        heads.append(he)
+                        extra_probs.append(pe)
+                    neg = eng.pool_matrices(negs, heads)
+                    import torch
+                    probs = [torch.tensor([pe[k] for pe in extra_probs] + [probs[k]]).mean(dim=0).tolist()     # timing.py:183-189
+                             for k in range(len(sub))]
+            paths = eng.dtw(neg, n_rows, frames)
+            jumps = [_path_jumps(text_idx, time_idx) for text_idx, time_idx in paths]
+        out.extend((probs[k], paths[k][0], paths[k][1]) for k in range(len(sub)))
+    return out
+
+
+def _find_alignment_variants_loop(model, jobs, xkv, *, medfilt_width, qk_scale, dynamic_heads, aligner, extra_models, mel):
+    """The same, one window at a time: ``score_q`` (the pass, keeping the cross-attention queries), ``heads_dynamic``
+    (timing.py:87-112), ``heads_new`` (timing.py:115-163), ``pool_matrices`` (timing.py:177-189) per window and iteration."""
+    from .transcribe import _xkv_select
+    _check_variant_args(model, aligner, extra_models)
     tok = jobs[0].tokenizer
     n_sot, eot = len(tok.sot_sequence), tok.eot
     count, iterations = parse_dynamic_heads(dynamic_heads)
