@@ -452,6 +452,22 @@ int swx_test_self_attn_plan(int dtype, int R, int H, int n_new, int n_ctx, int r
 /* which kernel swx_test_dec_gemm's launch gets (host-only, no GPU; the function swx_gemm_dec itself executes), `epilogue` as there:
  * 0 gemm_dec_f16 with four-wave workgroups, 1 with single-wave workgroups, 2 / 3 gemm_dectall_f16 with four / eight waves; < 0: not offered */
 int swx_test_dec_plan(int M, int N, int K, int epilogue, int flags);
+/* where the head-selection entries keep their intermediates (host-only, no GPU; the function the entries themselves carve their
+ * scratch with).  out[9] = byte offsets cnt, score, sel, colnorm, nscore, top, gathered, rstat and the total, which equals
+ * swx_heads_batch_scratch_bytes(m, W, max_n, count).  With LH = n_text_layer * n_text_head, R = max_n - n_sot - 1 (the row stride
+ * of a batch call) and 1536 = the frame stride of the column norms:
+ *   cnt      int32 [3][W]            n_tok | text rows | frames (clamped to [1, n_audio_ctx]) of every window
+ *   score    f64   [W][LH][R]        dynamic: head scores (timing.py:101), head l * n_text_head + h
+ *   sel      int32 [W][R][count]     dynamic: the picked heads of every row, best first
+ *   colnorm  f32   [W][LH][1536]     new: column norms over all n_tok rows, frames [0, F)
+ *   nscore   f32   [W][LH]           new: head scores (timing.py:143-155)
+ *   top      int32 [W][LH]           new: the first topk entries = the picked heads, best first
+ *   gathered f32   [W][count][R][n_audio_ctx]   dynamic: raw scaled scores of slot k of every row, frames [0, n_audio_ctx)
+ *   rstat    f32   [W][count][R][2]  dynamic: softmax row maximum and sum
+ * W = 0: the single-window layout of swx_heads_dynamic / swx_heads_new (total = swx_heads_scratch_bytes(m, max_n); count is not
+ * read): score [LH][n_rows] and sel [n_rows][count] with the call's own n_rows as the row stride, colnorm / nscore / top as above
+ * with W = 1; cnt, gathered and rstat are empty (their offsets are those of the region that follows). */
+int swx_test_heads_layout(const swx_model *m, int W, int max_n, int count, int64_t *out);
 
 /* the VALU lane-exchange helpers of csrc/swx_common.h (v_permlane16/32_swap, DPP) against __shfl_xor, on n_waves waves of 64
  * u32 values: d_out[((w * 13 + k) * 64) + lane], k = 0..5 lane_xor<32, 16, 8, 4, 2, 1>, k = 6..11 the __shfl_xor of the same

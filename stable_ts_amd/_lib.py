@@ -132,6 +132,7 @@ SYMBOLS = {
                                               c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "swx_test_self_attn_plan": (c_int, [c_int] * 12),
     "swx_test_dec_plan": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "swx_test_heads_layout": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_int64)]),
     "swx_test_gelu_pair": (c_int, [c_void_p, c_void_p]),
     "swx_test_decode_script_ws_bytes": (c_size_t, [POINTER(swx_decode_cfg), c_int, c_int]),
     "swx_test_decode_script": (c_int, [POINTER(swx_decode_cfg), c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -1931,13 +1931,35 @@ int swx_score_q(swx_model *m, const int32_t *d_tokens, const int32_t *h_n_tok, i
     return 0;
 }
 
-// scratch of the two calls below: head scores (f64) and picks of every row, column norms / scores / picks of every head
+// scratch of the head-selection calls, as byte offsets (every region 256-byte aligned; include/swx.h lists the shapes).  One
+// function lays out both forms and the launchers below carve their pointers from what it returns, so swx_test_heads_layout
+// reports the layout the code uses.  W >= 1: the two batch calls -- the per-window counts, then for W windows the head scores
+// (f64) and picks of every row, the column norms / scores / picks of every head, then (count > 0) the gathered raw scores
+// [W][count][max_rows][n_audio_ctx] f32 and the row statistics swx_align_weights_launch needs.  W == 0: the single-window calls
+// -- no counts, picks sized for count = LH, no gathered rows (the caller's d_qk_sel receives them) and no row statistics.
+struct HeadsBatchScratch { size_t cnt, score, sel, colnorm, nscore, top, gathered, rstat, total; };
+static HeadsBatchScratch heads_batch_layout(const swx_model *m, int W, int max_n, int count)
+{
+    const size_t LH = (size_t)m->dims.n_text_layer * m->dims.n_text_head, w = W > 0 ? (size_t)W : 1, c = count > 0 ? (size_t)count : 0;
+    HeadsBatchScratch L{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += align_up(bytes); return at; };
+    L.cnt = take(W > 0 ? 3 * w * sizeof(int32_t) : 0);
+    L.score = take(w * LH * max_n * sizeof(double));
+    L.sel = take(W > 0 ? w * max_n * (c ? c : 1) * sizeof(int32_t) : LH * max_n * sizeof(int32_t));
+    L.colnorm = take(w * LH * SWX_HS_MAXF * sizeof(float));
+    L.nscore = take(w * LH * sizeof(float));
+    L.top = take(w * LH * sizeof(int32_t));
+    L.gathered = take(W > 0 ? w * c * max_n * m->dims.n_audio_ctx * sizeof(float) : 0);
+    L.rstat = take(W > 0 ? w * c * max_n * sizeof(float2) : 0);
+    L.total = off;
+    return L;
+}
+
 size_t swx_heads_scratch_bytes(const swx_model *m, int max_n)
 {
     if (!m || max_n <= 0) return 0;
-    const size_t LH = (size_t)m->dims.n_text_layer * m->dims.n_text_head;
-    return align_up(LH * max_n * sizeof(double)) + align_up(LH * max_n * sizeof(int32_t)) + align_up(LH * SWX_HS_MAXF * sizeof(float)) +
-           align_up(LH * sizeof(float)) + align_up(LH * sizeof(int32_t));
+    return heads_batch_layout(m, 0, max_n, 0).total;
 }
 
 // dynamic_heads (timing.py:87-103): rows row0 .. row0 + n_rows - 1 of the pass; d_qk_sel [count][n_rows][ld_f] f32 receives the RAW
@@ -1952,10 +1974,10 @@ int swx_heads_dynamic(swx_model *m, const void *d_q, int max_n, int row0, int n_
     if (row0 < 0 || n_rows <= 0 || row0 + n_rows > max_n || ld_f < m->dims.n_audio_ctx) return -1;
     if (scratch_bytes < swx_heads_scratch_bytes(m, max_n)) return -8;
     const swx_dims &D = m->dims;
-    const size_t LH = (size_t)D.n_text_layer * D.n_text_head;
+    const HeadsBatchScratch L = heads_batch_layout(m, 0, max_n, 0);
     unsigned char *p = (unsigned char *)d_scratch;
-    double *score = (double *)p; p += align_up(LH * max_n * sizeof(double));
-    int32_t *sel = (int32_t *)p;
+    double *score = (double *)(p + L.score);
+    int32_t *sel = (int32_t *)(p + L.sel);
     int F = n_frames < 1 ? 1 : (n_frames > D.n_audio_ctx ? D.n_audio_ctx : n_frames);
     return swx_headsel_dynamic_launch(m->dtype, d_q, max_n, D.n_text_state, row0, n_rows, d_xkv, xkv_chunk_elems(m), D.n_text_layer,
                                       D.n_text_head, F, D.n_audio_ctx, qk_scale, count, d_peaks, score, sel, d_qk_sel, ld_f, S(stream));
@@ -1972,12 +1994,11 @@ int swx_heads_new(swx_model *m, const void *d_q, int max_n, int n_tok, int row0,
     if (n_tok <= 0 || n_tok > max_n) return -1;
     if (scratch_bytes < swx_heads_scratch_bytes(m, max_n)) return -8;
     const swx_dims &D = m->dims;
-    const size_t LH = (size_t)D.n_text_layer * D.n_text_head;
+    const HeadsBatchScratch L = heads_batch_layout(m, 0, max_n, 0);
     unsigned char *p = (unsigned char *)d_scratch;
-    p += align_up(LH * max_n * sizeof(double)) + align_up(LH * max_n * sizeof(int32_t));
-    float *colnorm = (float *)p; p += align_up(LH * SWX_HS_MAXF * sizeof(float));
-    float *score = (float *)p; p += align_up(LH * sizeof(float));
-    int32_t *top = (int32_t *)p;
+    float *colnorm = (float *)(p + L.colnorm);
+    float *score = (float *)(p + L.nscore);
+    int32_t *top = (int32_t *)(p + L.top);
     int F = n_frames < 1 ? 1 : (n_frames > D.n_audio_ctx ? D.n_audio_ctx : n_frames);
     return swx_headsel_new_launch(m->dtype, d_q, max_n, D.n_text_state, n_tok, row0, n_out, d_xkv, xkv_chunk_elems(m), D.n_text_layer,
                                   D.n_text_head, F, qk_scale, medfilt_width, topk, w_colnorm, w_rownorm, w_coverage, colnorm, score, top,
@@ -2006,26 +2027,6 @@ int swx_score_q_batch(swx_model *m, const int32_t *d_tokens, const int32_t *h_n_
     return 0;
 }
 
-// scratch of the two batch calls: the per-window counts, then per window what swx_heads_scratch_bytes lists, then (count > 0) the
-// gathered raw scores [W][count][max_rows][n_audio_ctx] f32 and the row statistics swx_align_weights_launch needs
-struct HeadsBatchScratch { size_t cnt, score, sel, colnorm, nscore, top, gathered, rstat, total; };
-static HeadsBatchScratch heads_batch_layout(const swx_model *m, int W, int max_n, int count)
-{
-    const size_t LH = (size_t)m->dims.n_text_layer * m->dims.n_text_head, w = (size_t)W, c = count > 0 ? (size_t)count : 0;
-    HeadsBatchScratch L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += align_up(bytes); return at; };
-    L.cnt = take(3 * w * sizeof(int32_t));
-    L.score = take(w * LH * max_n * sizeof(double));
-    L.sel = take(w * max_n * (c ? c : 1) * sizeof(int32_t));
-    L.colnorm = take(w * LH * SWX_HS_MAXF * sizeof(float));
-    L.nscore = take(w * LH * sizeof(float));
-    L.top = take(w * LH * sizeof(int32_t));
-    L.gathered = take(w * c * max_n * m->dims.n_audio_ctx * sizeof(float));
-    L.rstat = take(w * c * max_n * sizeof(float2));
-    L.total = off;
-    return L;
-}
 // validates the per-window counts and puts [n_tok | n_rows | n_frames (clamped to [1, n_audio_ctx])] at the head of the scratch
 static int heads_batch_counts(swx_model *m, int W, int max_n, int n_sot, const int32_t *h_n_tok, const int32_t *h_n_frames, int32_t *d_cnt,
                        hipStream_t s)
@@ -2329,6 +2330,16 @@ int swx_test_dec_plan(int M, int N, int K, int epilogue, int flags)
     int mt = 1, ks2 = 1;
     bool ticket = false;
     return swx_dec_kernel_plan(M, N, K, epilogue & 31, (epilogue & 64) ? 1 : 0, (epilogue & DEC_RES) != 0, flags, &mt, &ks2, &ticket);
+}
+
+int swx_test_heads_layout(const swx_model *m, int W, int max_n, int count, int64_t *out)
+{
+    // the byte offsets the head-selection entries carve out of their scratch: heads_batch_layout, the function they call themselves
+    if (!m || !out || W < 0 || max_n <= 0 || count < 0) return -1;
+    const HeadsBatchScratch L = heads_batch_layout(m, W, max_n, W > 0 ? count : 0);
+    const size_t v[9] = {L.cnt, L.score, L.sel, L.colnorm, L.nscore, L.top, L.gathered, L.rstat, L.total};
+    for (int k = 0; k < 9; ++k) out[k] = (int64_t)v[k];
+    return 0;
 }
 
 int swx_test_layernorm(int dtype, const void *d_x, const float *d_g, const float *d_b, void *d_y, int rows, int d, void *stream)
