@@ -363,7 +363,8 @@ int swx_dtw(const float *d_x, int W, int ld_n, int ld_m, const int32_t *d_N, con
  *          4 cached self-attention 5 select/beam 6 mel 7 align-weights 8 dtw 9 layernorm
  * swx_prof_collect: out[cls*3+{0,1,2}] = {launches, total ms, total algorithmic work}; returns the class count */
 int swx_prof_enable(int on);
-/* A/B switches for tests and scripts (SWX_FLAG_* in csrc/swx_kernels.h): 1 = decode steps and small passes through the general
+/* A/B switches for tests and scripts (SWX_FLAG_* = 1 << bit, all of them in SWX_FLAG_TABLE in csrc/swx_kernels.h, which fails the
+ * build when two share a bit; bits 0..30 only, because a negative argument is the query): 1 = decode steps and small passes through the general
  * per-op path instead of the fused "dec" step (its reference), 2048 = decode cross-attention on the row-layout K / V^T
  * (reference of the fragment-ordered copy), 8192 = memory-walking logit filters (reference of the register kernel),
  * 16384 = decode loop without the captured step graph, 32768 = decode step without the cache prefetch of the next projection's

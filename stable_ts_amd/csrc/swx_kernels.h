@@ -47,48 +47,75 @@ int swx_gemm_plan_f16(int M, int N, int K, int epi, int64_t ldc, int64_t ldr, bo
 //      selects the bit-identity / parity REFERENCE of a kernel class; the superseded generations these flags used to keep
 //      alive (split-K decode step, flash attention v1, DTW generation 2, the tiled-GEMM variants that lost) were deleted in
 //      round 3.
-#define SWX_FLAG_NO_FAST_STEP 1       // decode steps / small passes go through the generic per-op path (LayerNorm launches,
-                                      // row-major weights, skinny / tiled GEMMs): the reference of the fused "dec" step
-#define SWX_FLAG_NO_PACKED_XKV 2048   // decode cross-attention reads the row-layout K / V^T instead of the fragment-ordered copy
-#define SWX_FLAG_SELECT_MEM 8192      // logit filters + token selection: the kernel that walks the row in memory (reference of
-                                      // the register-resident kernel, and its fallback for vocabularies > 51 * 1024)
-#define SWX_FLAG_NO_GRAPH 16384       // decode loop: launch every step eagerly instead of replaying the captured two-step graph
-#define SWX_FLAG_NO_PREFETCH 32768    // decode step: no cache prefetch of the next projection's weights (A/B; no functional effect)
-#define SWX_FLAG_NO_RING 65536        // tiled GEMM: never the ring kernel for launches with few tiles (A/B; results are bit-identical)
-#define SWX_FLAG_SCORE_TILED 262144   // multi-token decoder passes above 160 rows on the tiled GEMMs + flash attention (round 3's
-                                      // dispatch: faster at >= 2 windows, but a window's rounding then depends on its batch) -- A/B only
-#define SWX_FLAG_NO_TALL 524288       // multi-token passes: never the tall dec GEMM (register-resident weights, 16-row tiles): A/B, bit-identical
-#define SWX_FLAG_NO_FUSED_XQ 1048576  // decode step: cross-attention query projection as a launch of its own instead of inside the
-                                      // cross-attention kernel (A/B; bit-identical)
-#define SWX_FLAG_TICKET 2097152       // decode step: the K-split projection's slabs reduced INSIDE the GEMM launch by the last-arriving K slice
-                                      // (DEC_TICKET) instead of by dec_slab_finish.  Built and measured in round 5 in two forms, both
-                                      // bit-identical: plain slab stores + agent-scope release / acquire fences 451.8 vs 432.6 ms per headline
-                                      // pass (the launch 17.0 us against 8.2 + 5.0); write-through `sc1` slab stores + drained ticket + `sc1`
-                                      // reads (the form kept) 432.4 vs 430.1 ms -- break-even at best, so off by default; kept for A/B
-                                      // (profiles/r05_c5_bench_ticket_ab.json, r05_c12_bench_ticket_sc1_ab.json).
-#define SWX_FLAG_BIG8_GROUPED 4194304 // 256 x 256 GEMM: tiles listed in groups of 4 column tiles walked along M instead of row-major (A/B;
-                                      // bit-identical).  Built in round 6 to cut the N = 5120 launch's 3.8x fabric traffic: measured neutral to
-                                      // 3 % SLOWER at every encoder shape (profiles/r06_c2_kb_gemm_big_tile_order.txt), so off by default
-#define SWX_FLAG_XKV_TWO_LAUNCHES 8388608 // cross-K/V projection as two launches (K, then V) instead of one over the fused weight rows (A/B; bit-identical)
-#define SWX_FLAG_LOUDNESS_ONE_WG 16777216  // silence analysis probe: always the one-workgroup-per-window selection kernel (A/B; the same element)
-#define SWX_FLAG_XATTN_R5 33554432     // decode cross-attention: one key block per wave in flight, default load policy (rounds 2-5) instead of two + nt (A/B; bit-identical)
-#define SWX_FLAG_FLASH_PIPELINED 67108864 // f16 flash attention: the software-pipelined tile attn_flash3_f16 (round 6: bit-identical, measured 4 % SLOWER than generation 2 -- DESIGN.md section 7) instead of attn_flash2_f16
-#define SWX_FLAG_SELFATTN_WG5 134217728  // decode-step self-attention: five rows (the beams of a window) per workgroup instead of one wave per workgroup (A/B; the same arithmetic per row)
-#define SWX_FLAG_QKV_SEPARATE_VT 268435456 // encoder at few windows: V transposed by its own launch instead of by the QKV projection's epilogue (A/B; bit-identical)
-#define SWX_FLAG_SELFATTN_NO_DEEP 4    // decode-step self-attention, long context at <= 1 024 waves: the chunk-by-chunk kernel instead of every load in two batches (A/B; bit-identical)
-#define SWX_FLAG_DEC_NO_W1 16           // decode-step GEMM at <= 80 workgroups: four-wave workgroups instead of single-wave ones (A/B; bit-identical)
-#define SWX_FLAG_TALL_NO_W8 32           // tall dec GEMM: four waves = one 64-column panel per workgroup (rounds 4-5) instead of eight waves = two panels (A/B; bit-identical)
-#define SWX_FLAG_SELFATTN_NO_MQ 256       // multi-token self-attention: one wave per (row, token, head) reading K / V from L2 (rounds 1-5) instead of 4-8 tokens per workgroup from LDS (A/B; bit-identical)
-#define SWX_FLAG_FLASH_NO_QB1 64           // f16 flash attention of launches with <= 256 workgroups at 32 queries per wave: 32 queries per wave (rounds 3-5) instead of 16 (A/B; bit-identical)
-#define SWX_FLAG_XKV_PACK_SEPARATE 128     // cross-K/V: the fragment-ordered copy by its own launch (swx_xkv_pack, rounds 2-5) instead of by the projection's epilogue (A/B; the same bytes)
-#define SWX_FLAG_DEC_W1_FULL_TILE 256     // single-wave dec GEMM workgroups: DMA all 16 rows of the activation tile (rows past M clamped) instead of the rows that exist (A/B; bit-identical)
-#define SWX_FLAG_XQ_FULL_TILE 512          // decode cross-attention's fused query projection: DMA all 16 rows of the residual tile instead of the window's nq rows (A/B; bit-identical)
-#define SWX_FLAG_KCACHE_CHUNKED 2      // f16 decode: the self-attention K cache in position-contiguous 16-byte chunks per head (KLayout below) instead of
-                                      // row-major [n_ctx][d] like the V cache.  Bit-identical.  Measured: the step kernel 9.67 vs 9.75 us in the headline
-                                      // pass, whose passes it does not separate (407.5-408.5 vs 406.2-407.4 ms); sequential mode 4 600-4 610 vs
-                                      // 4 650-4 689 ms; stand-alone 15 % slower when neighbouring keys come from different beams, 14 % faster when
-                                      // from one row.  Off by default (profiles/kcache_layout_*)
-#define SWX_FLAG_NO_BIG_TILE 131072   // tiled GEMM: never the 256 x 256 kernel (A/B; results are bit-identical)
+//      ONE list, (name, bit index) in bit order: SWX_FLAG_<name> = 1 << bit.  The static_asserts below it fail the build when two
+//      entries share a bit or an index leaves 0..30 (swx_debug_flags(-1) is the "read" sentinel, so bit 31 cannot be a switch).
+//      Free: 3, 12, 29, 30.  bench.py --debug-flags / --ab-flags, the tests and the recorded profiles name switches by their
+//      integers, so an entry keeps its bit for good.
+#define SWX_FLAG_TABLE(X) \
+    X(NO_FAST_STEP, 0)        /* decode steps / small passes go through the generic per-op path (LayerNorm launches, row-major weights, \
+                                 skinny / tiled GEMMs): the reference of the fused "dec" step */ \
+    X(KCACHE_CHUNKED, 1)      /* f16 decode: the self-attention K cache in position-contiguous 16-byte chunks per head (KLayout below) instead of \
+                                 row-major [n_ctx][d] like the V cache.  Bit-identical.  Measured: the step kernel 9.67 vs 9.75 us in the headline \
+                                 pass, whose passes it does not separate (407.5-408.5 vs 406.2-407.4 ms); sequential mode 4 600-4 610 vs \
+                                 4 650-4 689 ms; stand-alone 15 % slower when neighbouring keys come from different beams, 14 % faster when \
+                                 from one row.  Off by default (profiles/kcache_layout_*) */ \
+    X(SELFATTN_NO_DEEP, 2)    /* decode-step self-attention, long context at <= 1 024 waves: the chunk-by-chunk kernel instead of every load in \
+                                 two batches (A/B; bit-identical) */ \
+    X(DEC_NO_W1, 4)           /* decode-step GEMM at <= 80 workgroups: four-wave workgroups instead of single-wave ones (A/B; bit-identical) */ \
+    X(TALL_NO_W8, 5)          /* tall dec GEMM: four waves = one 64-column panel per workgroup (rounds 4-5) instead of eight waves = two panels \
+                                 (A/B; bit-identical) */ \
+    X(FLASH_NO_QB1, 6)        /* f16 flash attention of launches with <= 256 workgroups at 32 queries per wave: 32 queries per wave (rounds 3-5) \
+                                 instead of 16 (A/B; bit-identical) */ \
+    X(XKV_PACK_SEPARATE, 7)   /* cross-K/V: the fragment-ordered copy by its own launch (swx_xkv_pack, rounds 2-5) instead of by the \
+                                 projection's epilogue (A/B; the same bytes) */ \
+    X(SELFATTN_NO_MQ, 8)      /* multi-token self-attention: one wave per (row, token, head) reading K / V from L2 (rounds 1-5) instead of 4-8 \
+                                 tokens per workgroup from LDS (A/B; bit-identical) */ \
+    X(XQ_FULL_TILE, 9)        /* decode cross-attention's fused query projection: DMA all 16 rows of the residual tile instead of the window's \
+                                 nq rows (A/B; bit-identical) */ \
+    X(DEC_W1_FULL_TILE, 10)   /* single-wave dec GEMM workgroups: DMA all 16 rows of the activation tile (rows past M clamped) instead of the \
+                                 rows that exist (A/B; bit-identical).  Shared bit 8 with SELFATTN_NO_MQ when round 6 measured it */ \
+    X(NO_PACKED_XKV, 11)      /* decode cross-attention reads the row-layout K / V^T instead of the fragment-ordered copy */ \
+    X(SELECT_MEM, 13)         /* logit filters + token selection: the kernel that walks the row in memory (reference of the register-resident \
+                                 kernel, and its fallback for vocabularies > 51 * 1024) */ \
+    X(NO_GRAPH, 14)           /* decode loop: launch every step eagerly instead of replaying the captured two-step graph */ \
+    X(NO_PREFETCH, 15)        /* decode step: no cache prefetch of the next projection's weights (A/B; no functional effect) */ \
+    X(NO_RING, 16)            /* tiled GEMM: never the ring kernel for launches with few tiles (A/B; results are bit-identical) */ \
+    X(NO_BIG_TILE, 17)        /* tiled GEMM: never the 256 x 256 kernel (A/B; results are bit-identical) */ \
+    X(SCORE_TILED, 18)        /* multi-token decoder passes above 160 rows on the tiled GEMMs + flash attention (round 3's dispatch: faster at \
+                                 >= 2 windows, but a window's rounding then depends on its batch) -- A/B only */ \
+    X(NO_TALL, 19)            /* multi-token passes: never the tall dec GEMM (register-resident weights, 16-row tiles): A/B, bit-identical */ \
+    X(NO_FUSED_XQ, 20)        /* decode step: cross-attention query projection as a launch of its own instead of inside the cross-attention \
+                                 kernel (A/B; bit-identical) */ \
+    X(TICKET, 21)             /* decode step: the K-split projection's slabs reduced INSIDE the GEMM launch by the last-arriving K slice \
+                                 (DEC_TICKET) instead of by dec_slab_finish.  Built and measured in round 5 in two forms, both bit-identical: \
+                                 plain slab stores + agent-scope release / acquire fences 451.8 vs 432.6 ms per headline pass (the launch \
+                                 17.0 us against 8.2 + 5.0); write-through `sc1` slab stores + drained ticket + `sc1` reads (the form kept) \
+                                 432.4 vs 430.1 ms -- break-even at best, so off by default; kept for A/B \
+                                 (profiles/r05_c5_bench_ticket_ab.json, r05_c12_bench_ticket_sc1_ab.json). */ \
+    X(BIG8_GROUPED, 22)       /* 256 x 256 GEMM: tiles listed in groups of 4 column tiles walked along M instead of row-major (A/B; \
+                                 bit-identical).  Built in round 6 to cut the N = 5120 launch's 3.8x fabric traffic: measured neutral to 3 % \
+                                 SLOWER at every encoder shape (profiles/r06_c2_kb_gemm_big_tile_order.txt), so off by default */ \
+    X(XKV_TWO_LAUNCHES, 23)   /* cross-K/V projection as two launches (K, then V) instead of one over the fused weight rows (A/B; bit-identical) */ \
+    X(LOUDNESS_ONE_WG, 24)    /* silence analysis probe: always the one-workgroup-per-window selection kernel (A/B; the same element) */ \
+    X(XATTN_R5, 25)           /* decode cross-attention: one key block per wave in flight, default load policy (rounds 2-5) instead of two + nt \
+                                 (A/B; bit-identical) */ \
+    X(FLASH_PIPELINED, 26)    /* f16 flash attention: the software-pipelined tile attn_flash3_f16 (round 6: bit-identical, measured 4 % SLOWER \
+                                 than generation 2 -- DESIGN.md section 7) instead of attn_flash2_f16 */ \
+    X(SELFATTN_WG5, 27)       /* decode-step self-attention: five rows (the beams of a window) per workgroup instead of one wave per workgroup \
+                                 (A/B; the same arithmetic per row) */ \
+    X(QKV_SEPARATE_VT, 28)    /* encoder at few windows: V transposed by its own launch instead of by the QKV projection's epilogue (A/B; \
+                                 bit-identical) */
+#define SWX_FLAG_DEFINE(name, bit) constexpr int SWX_FLAG_##name = 1 << (bit);
+SWX_FLAG_TABLE(SWX_FLAG_DEFINE)
+#undef SWX_FLAG_DEFINE
+#define SWX_FLAG_IN_RANGE(name, bit) && (bit) >= 0 && (bit) <= 30
+#define SWX_FLAG_OR(name, bit) | (int64_t(1) << (bit))
+#define SWX_FLAG_SUM(name, bit) + (int64_t(1) << (bit))
+static_assert(true SWX_FLAG_TABLE(SWX_FLAG_IN_RANGE), "SWX_FLAG_TABLE: a bit index outside 0..30");
+static_assert((int64_t(0) SWX_FLAG_TABLE(SWX_FLAG_OR)) == (int64_t(0) SWX_FLAG_TABLE(SWX_FLAG_SUM)), "SWX_FLAG_TABLE: two switches share a bit");
+#undef SWX_FLAG_IN_RANGE
+#undef SWX_FLAG_OR
+#undef SWX_FLAG_SUM
 #define SWX_DEFAULT_FLAGS 0
 int swx_flags();
 

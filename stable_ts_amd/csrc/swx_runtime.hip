@@ -370,21 +370,28 @@ struct FwdCfg {
     bool xattn_by_blocks;  // strict f32: the cross-attention kernel must not depend on n_new (AttnArgs::f32_no_split)
 };
 
-// One decoder step (n_new == 1) in fp16: un-split "dec" GEMMs (swx_decstep.hip) that finish their own outputs.
-// 8 launches per layer (QKV+scatter, self-attention, out-proj+residual, cross-q, cross-attention, out-proj+residual, MLP-in+GELU,
-// MLP-out [+ its slab reduction]); no LayerNorm launch, no f32 slabs except for the K = 4d projection.  (The split-K
-// generation of rounds 1-2 -- 12 launches per layer -- was deleted in round 3; the generic per-op path below is the
-// bit-identity-free reference: SWX_FLAG_NO_FAST_STEP.)
+// The fused "dec" decoder layers in fp16, for both arms of decoder_forward: un-split "dec" GEMMs (swx_decstep.hip) that finish
+// their own outputs (bias / GELU / residual / K,V scatter, LayerNorm folded; no LayerNorm launch, no f32 slabs except for the
+// K = 4d projection).  8 launches per layer: QKV+scatter, self-attention, out-proj+residual, cross-q, cross-attention,
+// out-proj+residual, MLP-in+GELU, MLP-out [+ its slab reduction].  (The split-K generation of rounds 1-2 -- 12 launches per
+// layer -- was deleted in round 3; the generic per-op path below is the bit-identity-free reference: SWX_FLAG_NO_FAST_STEP.)
+//   step (n_new == 1, one token per row): the latency-optimised self-attention kernel over the cache, and the cross-q projection
+//     inside the cross-attention launch (7 launches) unless switched off.
+//   multi-token (teacher-forced pass over a SMALL number of rows: align(), one window of ~110 tokens; refine / locate probes; the
+//     prefill of a decode, W windows x the initial tokens, cache rows w * G): at <= 160 rows the tiled MFMA GEMM launches one or two
+//     row blocks and the 16-column skinny kernel 27 us per projection, while a dec launch finishes its outputs in ~7 us; from 161
+//     rows on the launcher takes the tall dec GEMM (DecGemmArgs::tall).  Self-attention (causal over the new tokens),
+//     cross-attention and the alignment-head capture are the general kernels.
 // Leaves the RAW residual stream in `x` (returns 0: the caller applies the final LayerNorm).
-int decoder_step_dec(swx_model *m, const FwdCfg &f, hipStream_t s)
+int decoder_dec(swx_model *m, const FwdCfg &f, hipStream_t s)
 {
     const swx_dims &D = m->dims;
     const int d = D.n_text_state, H = D.n_text_head;
     const size_t e = m->esz;
-    const int rows = f.W * f.rpw;
+    const bool step = f.n_new == 1;           // decoder_forward's step arm (row_mul 1, no capture, <= 16 rows per window)
+    const int R = f.W * f.rpw, rows = R * f.n_new, nq = f.rpw * f.n_new;
     f16 *x = m->Wp<f16>(m->L.x), *q = m->Wp<f16>(m->L.qkv), *att = m->Wp<f16>(m->L.att), *u = m->Wp<f16>(m->L.u);
-    float *slabs = m->Wp<float>(m->L.slabs);
-    SWX_TRY(swx_embed(m->dtype, f.tokens, f.ld_tok, nullptr, f.pos0, rows, 1, m->arena + m->o_tok_emb,
+    SWX_TRY(swx_embed(m->dtype, f.tokens, f.ld_tok, nullptr, f.pos0, R, f.n_new, m->arena + m->o_tok_emb,
                       m->A<float>(m->o_dec_pos), d, x, s));
     const int64_t chunk = xkv_chunk_elems(m);
     // Prefetch chain (DecPrefetch, swx_kernels.h): each projection touches the weights of the NEXT projection.  What the
@@ -399,118 +406,40 @@ int decoder_step_dec(swx_model *m, const FwdCfg &f, hipStream_t s)
     auto pf_of = [&](size_t w_off, int N, int K, int epi) {
         return pf_on ? swx_dec_prefetch_of(m->A<f16>(w_off), rows, N, K, epi) : DecPrefetch{};
     };
-    for (int l = 0; l < D.n_text_layer; ++l) {
-        const LayerW &w = m->dec[l];
-        f16 *kc = (f16 *)(f.kcache + (size_t)l * f.layer_stride), *vc = (f16 *)(f.vcache + (size_t)l * f.layer_stride);
+    // one projection over all rows: out = epi(A W^T) with W packed [N][K]; DEC_RES accumulates into `out` (X), else `out` is C
+    auto proj = [&](const f16 *A, int64_t lda, size_t w_off, int N, int K, int epi, size_t c1_off, size_t c2_off, f16 *out, DecPrefetch pf) {
         DecGemmArgs g{};
-        g.M = rows;
-        // q | k | v = LN1(x) Wqkv^T + b : q -> the q buffer, k / v -> the cache at each row's position
-        g.A = x; g.lda = d; g.W = m->A<f16>(w.wqkv_f); g.ldw = d; g.N = 3 * d; g.K = d; g.epi = DEC_LN | DEC_QKV;
-        g.c1 = m->A<float>(w.qkv_c1); g.c2 = m->A<float>(w.qkv_c2); g.C = q; g.ldc = d;
-        g.kcache = kc; g.vcache = vc; g.pos0 = f.pos0; g.n_ctx = D.n_text_ctx; g.d = d;
-        g.kl = swx_klayout(f.k_chunked, D.n_text_ctx, d);
-        g.pf = pf_of(w.wo_p, d, d, DEC_RES);                 // used after the self-attention (<= 57 MB through the cache)
-        SWX_TRY(swx_gemm_dec(g, s));
-        SelfAttnArgs sa{};
-        sa.qkv = q; sa.ldqkv = d; sa.kcache = kc; sa.vcache = vc; sa.anc = f.anc; sa.pos0 = f.pos0; sa.o = att; sa.ldo = d;
-        sa.R = rows; sa.n_new = 1; sa.H = H; sa.n_ctx = D.n_text_ctx; sa.d = d; sa.skip_append = 1; sa.step_cached = 1;
-        sa.step_pos = f.step_pos; sa.pos_bound = f.pos_bound; sa.kl = g.kl;
-        SWX_TRY(swx_self_attention(m->dtype, sa, 1, s));
-        // x += att Wo^T + bo
-        g = DecGemmArgs{};
-        g.M = rows; g.A = att; g.lda = d; g.W = m->A<f16>(w.wo_p); g.ldw = d; g.N = d; g.K = d; g.epi = DEC_RES;
-        g.c2 = m->A<float>(w.bo); g.X = x; g.ldx = d;
-        g.pf = pf_of(w.wcq_f, d, d, DEC_LN);
-        SWX_TRY(swx_gemm_dec(g, s));
-        // cross-attention query = LNx(x) Wcq^T + b: inside the cross-attention launch (AttnArgs::fq_*) unless switched off
-        const bool fuse_xq = !(g_debug_flags & (SWX_FLAG_NO_FUSED_XQ | SWX_FLAG_NO_PACKED_XKV)) && f.rpw <= 16 && d % 128 == 0 &&
-                             (d == 384 || d == 512 || d == 640 || d == 768 || d == 1024 || d == 1280);
-        if (!fuse_xq) {
-            g = DecGemmArgs{};
-            g.M = rows; g.A = x; g.lda = d; g.W = m->A<f16>(w.wcq_f); g.ldw = d; g.N = d; g.K = d; g.epi = DEC_LN;
-            g.c1 = m->A<float>(w.cq_c1); g.c2 = m->A<float>(w.cq_c2); g.C = q; g.ldc = d;
-            g.pf = pf_of(w.wco_p, d, d, DEC_RES);                // used after the cross-attention (154 MB through the cache)
-            SWX_TRY(swx_gemm_dec(g, s));
-        }
-        const unsigned char *kl = f.xkv + (size_t)l * (f.xkv_W ? f.xkv_W : f.W) * chunk * e;
-        AttnArgs ca{};
-        ca.q = q; ca.ldq = d; ca.k = kl; ca.v = kl + (size_t)D.n_audio_ctx * d * e; ca.ldkv = d;
-        ca.k_bs = chunk; ca.v_bs = chunk; ca.vt_kp = SWX_VT_KP; ca.o = att; ca.ldo = d;
-        ca.B = f.W; ca.H = H; ca.nq = f.rpw; ca.nk = D.n_audio_ctx; ca.q_rows_per_batch = f.rpw;
-        ca.kv_packed = kl + (size_t)xkv_plain_elems(D) * e;          // fragment-ordered copy of this layer's K / V^T
-        if (fuse_xq) {
-            ca.fq_x = x; ca.fq_ldx = d; ca.fq_rows = rows; ca.fq_w = m->A<f16>(w.wcq_f); ca.fq_c1 = m->A<float>(w.cq_c1);
-            ca.fq_c2 = m->A<float>(w.cq_c2); ca.fq_k = d;
-            if (pf_on) { ca.fq_pf = m->A<f16>(w.wco_p); ca.fq_pf_lines = (int)(((int64_t)d * d * 2) >> 7); }
-        }
-        SWX_TRY(swx_attention(m->dtype, ca, 0, s));
-        g = DecGemmArgs{};
-        g.M = rows; g.A = att; g.lda = d; g.W = m->A<f16>(w.wco_p); g.ldw = d; g.N = d; g.K = d; g.epi = DEC_RES;
-        g.c2 = m->A<float>(w.bco); g.X = x; g.ldx = d;
-        g.pf = pf_of(w.w1_f, 4 * d, d, DEC_LN | DEC_GELU);
-        SWX_TRY(swx_gemm_dec(g, s));
-        // MLP
-        g = DecGemmArgs{};
-        g.M = rows; g.A = x; g.lda = d; g.W = m->A<f16>(w.w1_f); g.ldw = d; g.N = 4 * d; g.K = d; g.epi = DEC_LN | DEC_GELU;
-        g.c1 = m->A<float>(w.w1_c1); g.c2 = m->A<float>(w.w1_c2); g.C = u; g.ldc = 4 * d;
-        g.pf = pf_of(w.w2_p, d, 4 * d, DEC_RES | DEC_SLAB);
-        SWX_TRY(swx_gemm_dec(g, s));
-        g = DecGemmArgs{};
-        g.M = rows; g.A = u; g.lda = 4 * d; g.W = m->A<f16>(w.w2_p); g.ldw = 4 * d; g.N = d; g.K = 4 * d; g.epi = DEC_RES | DEC_SLAB;
-        g.c2 = m->A<float>(w.b2); g.X = x; g.ldx = d; g.slabs = slabs; g.ticket = m->Wp<int>(m->L.ticket);
-        if (l + 1 < D.n_text_layer) g.pf = pf_of(m->dec[l + 1].wqkv_f, 3 * d, d, DEC_LN | DEC_QKV);
-        SWX_TRY(swx_gemm_dec(g, s));
-    }
-    return 0;
-}
-
-// Multi-token teacher-forced pass over a SMALL number of rows (align(): one window of ~110 tokens; refine / locate probes; the
-// prefill of a decode: W windows x the initial tokens, cache rows w * G) on
-// the same un-split "dec" GEMMs as the decode step: at <= 160 rows the tiled MFMA GEMM launches one or two row blocks and the
-// 16-column skinny kernel 27 us per projection, while a dec launch finishes its outputs (bias / GELU / residual / K,V scatter,
-// LayerNorm folded) in ~7 us.  Self-attention (causal over the new tokens), cross-attention and the alignment-head capture are
-// the general kernels.  Leaves the raw residual stream in `x` (returns 0).
-int decoder_forward_dec(swx_model *m, const FwdCfg &f, hipStream_t s)
-{
-    const swx_dims &D = m->dims;
-    const int d = D.n_text_state, H = D.n_text_head;
-    const size_t e = m->esz;
-    const int R = f.W * f.rpw, rows = R * f.n_new;
-    f16 *x = m->Wp<f16>(m->L.x), *q = m->Wp<f16>(m->L.qkv), *att = m->Wp<f16>(m->L.att), *u = m->Wp<f16>(m->L.u);
-    float *slabs = m->Wp<float>(m->L.slabs);
-    SWX_TRY(swx_embed(m->dtype, f.tokens, f.ld_tok, nullptr, f.pos0, R, f.n_new, m->arena + m->o_tok_emb,
-                      m->A<float>(m->o_dec_pos), d, x, s));
-    const int64_t chunk = xkv_chunk_elems(m);
-    const bool pf_on = !(g_debug_flags & SWX_FLAG_NO_PREFETCH) && rows >= 32;       // the decode step's prefetch chain (decoder_step_dec)
-    auto pf_of = [&](size_t w_off, int N, int K, int epi) {
-        return pf_on ? swx_dec_prefetch_of(m->A<f16>(w_off), rows, N, K, epi) : DecPrefetch{};
+        g.M = rows; g.tall = step ? 0 : 1; g.A = A; g.lda = lda; g.W = m->A<f16>(w_off); g.ldw = K; g.N = N; g.K = K; g.epi = epi;
+        if (epi & DEC_LN) g.c1 = m->A<float>(c1_off);
+        g.c2 = m->A<float>(c2_off);
+        if (epi & DEC_RES) { g.X = out; g.ldx = N; } else { g.C = out; g.ldc = (epi & DEC_QKV) ? N / 3 : N; }
+        g.pf = pf;
+        return g;
     };
     for (int l = 0; l < D.n_text_layer; ++l) {
         const LayerW &w = m->dec[l];
         f16 *kc = (f16 *)(f.kcache + (size_t)l * f.layer_stride), *vc = (f16 *)(f.vcache + (size_t)l * f.layer_stride);
-        DecGemmArgs g{};
-        g.M = rows; g.tall = 1; g.A = x; g.lda = d; g.W = m->A<f16>(w.wqkv_f); g.ldw = d; g.N = 3 * d; g.K = d; g.epi = DEC_LN | DEC_QKV;
-        g.c1 = m->A<float>(w.qkv_c1); g.c2 = m->A<float>(w.qkv_c2); g.C = q; g.ldc = d;
+        // q | k | v = LN1(x) Wqkv^T + b : q -> the q buffer, k / v -> the cache at each row's position
+        DecGemmArgs g = proj(x, d, w.wqkv_f, 3 * d, d, DEC_LN | DEC_QKV, w.qkv_c1, w.qkv_c2, q,
+                             pf_of(w.wo_p, d, d, DEC_RES));          // used after the self-attention (<= 57 MB through the cache)
         g.kcache = kc; g.vcache = vc; g.pos0 = f.pos0; g.n_ctx = D.n_text_ctx; g.d = d; g.rps = f.n_new; g.row_mul = f.row_mul;
         g.kl = swx_klayout(f.k_chunked, D.n_text_ctx, d);
-        g.pf = pf_of(w.wo_p, d, d, DEC_RES);
         SWX_TRY(swx_gemm_dec(g, s));
         SelfAttnArgs sa{};
         sa.qkv = q; sa.ldqkv = d; sa.kcache = kc; sa.vcache = vc; sa.anc = f.anc; sa.pos0 = f.pos0; sa.o = att; sa.ldo = d;
         sa.R = R; sa.n_new = f.n_new; sa.H = H; sa.n_ctx = D.n_text_ctx; sa.d = d; sa.skip_append = 1; sa.kl = g.kl;
-        sa.pos0_all_zero = f.pos0 == m->Wp<int32_t>(m->L.zeros_i32) ? 1 : 0;
+        if (step) { sa.step_cached = 1; sa.step_pos = f.step_pos; sa.pos_bound = f.pos_bound; }
+        else sa.pos0_all_zero = f.pos0 == m->Wp<int32_t>(m->L.zeros_i32) ? 1 : 0;
         SWX_TRY(swx_self_attention(m->dtype, sa, f.row_mul, s));
-        g = DecGemmArgs{};
-        g.M = rows; g.tall = 1; g.A = att; g.lda = d; g.W = m->A<f16>(w.wo_p); g.ldw = d; g.N = d; g.K = d; g.epi = DEC_RES;
-        g.c2 = m->A<float>(w.bo); g.X = x; g.ldx = d;
-        g.pf = pf_of(w.wcq_f, d, d, DEC_LN);
-        SWX_TRY(swx_gemm_dec(g, s));
-        g = DecGemmArgs{};
-        g.M = rows; g.tall = 1; g.A = x; g.lda = d; g.W = m->A<f16>(w.wcq_f); g.ldw = d; g.N = d; g.K = d; g.epi = DEC_LN;
-        g.c1 = m->A<float>(w.cq_c1); g.c2 = m->A<float>(w.cq_c2); g.C = q; g.ldc = d;
-        g.pf = pf_of(w.wco_p, d, d, DEC_RES);
-        SWX_TRY(swx_gemm_dec(g, s));
-        if (f.qcap) {
+        // x += att Wo^T + bo
+        SWX_TRY(swx_gemm_dec(proj(att, d, w.wo_p, d, d, DEC_RES, 0, w.bo, x, pf_of(w.wcq_f, d, d, DEC_LN)), s));
+        // cross-attention query = LNx(x) Wcq^T + b: on the step arm inside the cross-attention launch (AttnArgs::fq_*) unless switched off
+        const bool fuse_xq = step && !(g_debug_flags & (SWX_FLAG_NO_FUSED_XQ | SWX_FLAG_NO_PACKED_XKV)) && f.rpw <= 16 && d % 128 == 0 &&
+                             (d == 384 || d == 512 || d == 640 || d == 768 || d == 1024 || d == 1280);
+        if (!fuse_xq)
+            SWX_TRY(swx_gemm_dec(proj(x, d, w.wcq_f, d, d, DEC_LN, w.cq_c1, w.cq_c2, q,
+                                      pf_of(w.wco_p, d, d, DEC_RES)), s));    // used after the cross-attention (154 MB through the cache)
+        if (f.qcap && !step) {
             hipError_t qe = hipMemcpyAsync(f.qcap + (size_t)l * rows * d * e, q, (size_t)rows * d * e, hipMemcpyDeviceToDevice, s);
             if (qe != hipSuccess) return -100 - (int)qe;
         }
@@ -518,28 +447,27 @@ int decoder_forward_dec(swx_model *m, const FwdCfg &f, hipStream_t s)
         AttnArgs ca{};
         ca.q = q; ca.ldq = d; ca.k = kl; ca.v = kl + (size_t)D.n_audio_ctx * d * e; ca.ldkv = d;
         ca.k_bs = chunk; ca.v_bs = chunk; ca.vt_kp = SWX_VT_KP; ca.o = att; ca.ldo = d;
-        ca.B = f.W; ca.H = H; ca.nq = f.rpw * f.n_new; ca.nk = D.n_audio_ctx; ca.q_rows_per_batch = f.rpw * f.n_new;
-        ca.kv_packed = kl + (size_t)xkv_plain_elems(D) * e;          // lets a small pass run as 16-row groups on the decode kernel
+        ca.B = f.W; ca.H = H; ca.nq = nq; ca.nk = D.n_audio_ctx; ca.q_rows_per_batch = nq;
+        ca.kv_packed = kl + (size_t)xkv_plain_elems(D) * e;          // fragment-ordered copy of this layer's K / V^T (also lets a
+                                                                     // small multi-token pass run as 16-row groups on the decode kernel)
+        if (fuse_xq) {
+            ca.fq_x = x; ca.fq_ldx = d; ca.fq_rows = rows; ca.fq_w = m->A<f16>(w.wcq_f); ca.fq_c1 = m->A<float>(w.cq_c1);
+            ca.fq_c2 = m->A<float>(w.cq_c2); ca.fq_k = d;
+            if (pf_on) { ca.fq_pf = m->A<f16>(w.wco_p); ca.fq_pf_lines = (int)(((int64_t)d * d * 2) >> 7); }
+        }
         SWX_TRY(swx_attention(m->dtype, ca, 0, s));
-        if (f.capture && !m->heads_by_layer[l].empty()) {
-            SWX_TRY(swx_qk_capture(m->dtype, q, d, f.rpw * f.n_new, f.cap_row0, f.cap_rows, kl, d, chunk, D.n_audio_ctx,
+        if (f.capture && !m->heads_by_layer[l].empty()) {           // never on the step arm: decoder_forward sends a capture elsewhere
+            SWX_TRY(swx_qk_capture(m->dtype, q, d, nq, f.cap_row0, f.cap_rows, kl, d, chunk, D.n_audio_ctx,
                                    m->Wp<int32_t>(m->L.heads) + m->head_slot0[l], (int)m->heads_by_layer[l].size(),
                                    m->head_slot0[l], m->n_align, f.W, m->Wp<float>(m->L.cap), f.cap_ld_n, D.n_audio_ctx, s));
         }
-        g = DecGemmArgs{};
-        g.M = rows; g.tall = 1; g.A = att; g.lda = d; g.W = m->A<f16>(w.wco_p); g.ldw = d; g.N = d; g.K = d; g.epi = DEC_RES;
-        g.c2 = m->A<float>(w.bco); g.X = x; g.ldx = d;
-        g.pf = pf_of(w.w1_f, 4 * d, d, DEC_LN | DEC_GELU);
-        SWX_TRY(swx_gemm_dec(g, s));
-        g = DecGemmArgs{};
-        g.M = rows; g.tall = 1; g.A = x; g.lda = d; g.W = m->A<f16>(w.w1_f); g.ldw = d; g.N = 4 * d; g.K = d; g.epi = DEC_LN | DEC_GELU;
-        g.c1 = m->A<float>(w.w1_c1); g.c2 = m->A<float>(w.w1_c2); g.C = u; g.ldc = 4 * d;
-        g.pf = pf_of(w.w2_p, d, 4 * d, DEC_RES | DEC_SLAB);
-        SWX_TRY(swx_gemm_dec(g, s));
-        g = DecGemmArgs{};
-        g.M = rows; g.tall = 1; g.A = u; g.lda = 4 * d; g.W = m->A<f16>(w.w2_p); g.ldw = 4 * d; g.N = d; g.K = 4 * d; g.epi = DEC_RES | DEC_SLAB;
-        g.c2 = m->A<float>(w.b2); g.X = x; g.ldx = d; g.slabs = slabs; g.ticket = m->Wp<int>(m->L.ticket);
-        if (l + 1 < D.n_text_layer) g.pf = pf_of(m->dec[l + 1].wqkv_f, 3 * d, d, DEC_LN | DEC_QKV);
+        SWX_TRY(swx_gemm_dec(proj(att, d, w.wco_p, d, d, DEC_RES, 0, w.bco, x, pf_of(w.w1_f, 4 * d, d, DEC_LN | DEC_GELU)), s));
+        // MLP
+        SWX_TRY(swx_gemm_dec(proj(x, d, w.w1_f, 4 * d, d, DEC_LN | DEC_GELU, w.w1_c1, w.w1_c2, u,
+                                  pf_of(w.w2_p, d, 4 * d, DEC_RES | DEC_SLAB)), s));
+        g = proj(u, 4 * d, w.w2_p, d, 4 * d, DEC_RES | DEC_SLAB, 0, w.b2, x,
+                 l + 1 < D.n_text_layer ? pf_of(m->dec[l + 1].wqkv_f, 3 * d, d, DEC_LN | DEC_QKV) : DecPrefetch{});
+        g.slabs = m->Wp<float>(m->L.slabs); g.ticket = m->Wp<int>(m->L.ticket);
         SWX_TRY(swx_gemm_dec(g, s));
     }
     return 0;
@@ -556,10 +484,10 @@ int decoder_forward(swx_model *m, const FwdCfg &f, hipStream_t s)
     const int64_t rows_all = (int64_t)f.W * f.rpw * f.n_new;
     if (dec_ok && f.n_new > 1 && (rows_all <= 160 || !(g_debug_flags & SWX_FLAG_SCORE_TILED)) && rows_all <= m->L.rows_big &&
         swx_dec_slab_floats((int)rows_all, m->dims.n_text_state, 4 * m->dims.n_text_state) * 4 <= m->L.slab_bytes)
-        return decoder_forward_dec(m, f, s);
+        return decoder_dec(m, f, s);
     if (dec_ok && f.n_new == 1 && f.row_mul == 1 && !f.capture && f.rpw <= 16 && m->dims.n_audio_ctx >= 128 &&
         (size_t)f.W * f.rpw <= (size_t)m->L.rows_big)
-        return decoder_step_dec(m, f, s);
+        return decoder_dec(m, f, s);
     const swx_dims &D = m->dims;
     const int d = D.n_text_state, H = D.n_text_head;
     const size_t e = m->esz;
@@ -619,6 +547,13 @@ int logits_gemm(swx_model *m, const void *hid, int64_t ld, int rows, float *out,
     const swx_dims &D = m->dims;
     return swx_gemm(m->dtype, gemm_args(hid, ld, m->arena + m->o_tok_emb, D.n_text_state, nullptr, out, D.n_vocab, rows,
                                         D.n_vocab, D.n_text_state, EPI_OUT_F32), 0, s);
+}
+
+// the decoder's final LayerNorm: `rows` contiguous rows of the raw residual stream at `src` -> the h buffer
+int final_ln(swx_model *m, const void *src, int rows, hipStream_t s)
+{
+    const int d = m->dims.n_text_state;
+    return swx_layernorm(m->dtype, src, d, m->A<float>(m->o_ln_g), m->A<float>(m->o_ln_b), m->ws + m->L.h, d, rows, d, s);
 }
 
 
@@ -1591,7 +1526,7 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
         if (fr < 0) return fr;
         unsigned char *hh = m->ws + m->L.h;
         if (fr == 0)   // the step leaves the raw residual stream in x
-            SWX_TRY(swx_layernorm(m->dtype, x, d, m->A<float>(m->o_ln_g), m->A<float>(m->o_ln_b), hh, d, M, d, st));
+            SWX_TRY(final_ln(m, x, M, st));
         SWX_TRY(logits_gemm(m, hh, d, M, b.logits, st));
         return swx_decode_select(b, cur_in, st);
     };
@@ -1684,7 +1619,7 @@ static int score_token_probs(swx_model *m, const int32_t *d_tokens, int W, int m
     const size_t e = m->esz;
     unsigned char *x = m->ws + m->L.x, *hh = m->ws + m->L.h;
     const int rows = W * max_n;
-    SWX_TRY(swx_layernorm(m->dtype, x, d, m->A<float>(m->o_ln_g), m->A<float>(m->o_ln_b), hh, d, rows, d, s));
+    SWX_TRY(final_ln(m, x, rows, s));
     const int rpw = max_n - n_sot - 2;     // probability rows per window (T_max)
     if (rpw > 0) {
         float *lg = m->Wp<float>(m->L.logits);
@@ -1772,7 +1707,7 @@ int swx_forward_logits(swx_model *m, const int32_t *d_tokens, const int32_t *h_n
     SWX_TRY(score_forward(m, d_tokens, h_n_tok, W, max_n, 0, 0, max_n, d_xkv, false, s));
     unsigned char *x = m->ws + m->L.x, *hh = m->ws + m->L.h;
     const int rows = W * max_n;
-    SWX_TRY(swx_layernorm(m->dtype, x, d, m->A<float>(m->o_ln_g), m->A<float>(m->o_ln_b), hh, d, rows, d, s));
+    SWX_TRY(final_ln(m, x, rows, s));
     return logits_gemm(m, hh, d, rows, d_logits, s);
 }
 
@@ -1793,7 +1728,7 @@ int swx_forward_token_ranks(swx_model *m, const int32_t *d_tokens, const int32_t
     const size_t e = m->esz;
     SWX_TRY(score_forward(m, d_tokens, h_n_tok, W, max_n, 0, 0, max_n, d_xkv, false, s));
     unsigned char *x = m->ws + m->L.x, *hh = m->ws + m->L.h;
-    SWX_TRY(swx_layernorm(m->dtype, x, d, m->A<float>(m->o_ln_g), m->A<float>(m->o_ln_b), hh, d, W * max_n, d, s));
+    SWX_TRY(final_ln(m, x, W * max_n, s));
     float *lg = m->Wp<float>(m->L.logits);
     // a fixed chunk (the logits region always holds 64 rows): the projection's launch shapes then depend on the window's own
     // token count alone, never on the workspace that happens to be bound or on the batch around the window
@@ -1863,7 +1798,7 @@ int swx_forward_next_token(swx_model *m, const int32_t *d_tokens, const int32_t 
         hipLaunchKernelGGL(gather_rows_kernel, dim3(nw), dim3(256), 0, s, (const uint4 *)x, (uint4 *)(last + (size_t)w0 * d * e), n16, rows);
         SWX_CHECK_LAUNCH();
     }
-    SWX_TRY(swx_layernorm(m->dtype, last, d, m->A<float>(m->o_ln_g), m->A<float>(m->o_ln_b), hh, d, W, d, s));
+    SWX_TRY(final_ln(m, last, W, s));
     float *lg = m->Wp<float>(m->L.logits);
     const int chunk = 64;
     for (int r0 = 0; r0 < W; r0 += chunk) {
@@ -1898,7 +1833,7 @@ int swx_detect_language(swx_model *m, const void *d_xkv, int W, int sot, const i
     const std::vector<int32_t> ones((size_t)W, 1);
     SWX_TRY(score_forward(m, d_tok, ones.data(), W, 1, 0, 0, 1, d_xkv, false, s));
     unsigned char *x = m->ws + m->L.x, *hh = m->ws + m->L.h;
-    SWX_TRY(swx_layernorm(m->dtype, x, d, m->A<float>(m->o_ln_g), m->A<float>(m->o_ln_b), hh, d, W, d, s));
+    SWX_TRY(final_ln(m, x, W, s));
     if (m->dtype == SWX_F16)
         hipLaunchKernelGGL(lang_id_kernel<f16>, dim3(W), dim3(256), lds, s, (const f16 *)hh, (const f16 *)(m->arena + m->o_tok_emb), d,
                            D.n_vocab, d_lang_tokens, n_lang, d_probs, d_best);

@@ -565,15 +565,8 @@ def test_dec_gemm_slab_reduction_inside_the_launch_is_bit_identical(M, N, K):
         lib.swx_debug_flags(prev)
 
 
-@pytest.mark.parametrize("M,N,K", [(5, 1280, 1280), (5, 3840, 1280), (5, 5120, 1280), (5, 1280, 5120), (1, 384, 384), (16, 512, 2048),
-                                   (10, 768, 768), (13, 1024, 4096), (60, 1280, 1280), (40, 1280, 1280), (33, 512, 512), (17, 384, 1536)])
-def test_dec_gemm_single_wave_workgroups_are_bit_identical(M, N, K):
-    # round 6: launches of at most 80 four-wave workgroups with one row tile per workgroup (the 5 rows of a sequential window's decode step;
-    # several row groups: the 60 rows of a 20-window prefill at N = 1280) run
-    # the same waves as SINGLE-wave workgroups (gemm_dec_f16<1, NKS, EPI, WPB = 1>: four times as many CUs share the weight stream);
-    # flag 16 = SWX_FLAG_DEC_NO_W1 puts the four-wave workgroups back.  Every epilogue the decode step uses: equal bits.
-    lib = _lib()
-    rng = np.random.default_rng(M * 7 + N + K)
+def _dec_step_cases(rng, M, N, K):
+    # inputs of an A/B of the decode-step GEMM and every epilogue the decode step uses on that shape: (name, _dec_gemm arguments, output)
     a = (rng.standard_normal((M, K)) * rng.uniform(0.5, 2.0, (M, 1)) + rng.uniform(-1, 1, (M, 1))).astype(np.float32) * 0.5
     w = rng.standard_normal((N, K)).astype(np.float32) * 0.03
     b = rng.standard_normal(N).astype(np.float32) * 0.1
@@ -586,6 +579,18 @@ def test_dec_gemm_single_wave_workgroups_are_bit_identical(M, N, K):
         if N % 3 == 0 and N // 3 == K:
             b3 = b.copy(); b3[K:2 * K] = 0.0
             cases += [("qkv", dict(gamma=gamma, beta=beta, bias=b3, epi=1 | 8, d=K, n_ctx=8, pos0=rng.integers(0, 8, M)), None)]
+    return a, w, cases
+
+
+@pytest.mark.parametrize("M,N,K", [(5, 1280, 1280), (5, 3840, 1280), (5, 5120, 1280), (5, 1280, 5120), (1, 384, 384), (16, 512, 2048),
+                                   (10, 768, 768), (13, 1024, 4096), (60, 1280, 1280), (40, 1280, 1280), (33, 512, 512), (17, 384, 1536)])
+def test_dec_gemm_single_wave_workgroups_are_bit_identical(M, N, K):
+    # round 6: launches of at most 80 four-wave workgroups with one row tile per workgroup (the 5 rows of a sequential window's decode step;
+    # several row groups: the 60 rows of a 20-window prefill at N = 1280) run
+    # the same waves as SINGLE-wave workgroups (gemm_dec_f16<1, NKS, EPI, WPB = 1>: four times as many CUs share the weight stream);
+    # flag 16 = SWX_FLAG_DEC_NO_W1 puts the four-wave workgroups back.  Every epilogue the decode step uses: equal bits.
+    lib = _lib()
+    a, w, cases = _dec_step_cases(np.random.default_rng(M * 7 + N + K), M, N, K)
     prev = lib.swx_debug_flags(-1)
     try:
         for name, kw, key in cases:
@@ -593,6 +598,36 @@ def test_dec_gemm_single_wave_workgroups_are_bit_identical(M, N, K):
             got = _dec_gemm(a, w, **kw)
             lib.swx_debug_flags(prev | 16)
             ref = _dec_gemm(a, w, **kw)
+            for k in ([key] if key else ["c", "kcache", "vcache"]):
+                assert np.isfinite(got[k]).all() and np.abs(got[k]).max() > 0, (name, k)
+                assert np.array_equal(got[k], ref[k]), (name, k, float(np.abs(got[k] - ref[k]).max()))
+    finally:
+        lib.swx_debug_flags(prev)
+
+
+_W1_FULL_TILE = 1024          # SWX_FLAG_DEC_W1_FULL_TILE
+_W1_ROWS_SHAPES = [(M, N, K) for N, K in ((384, 384), (1280, 1280), (3840, 1280), (1280, 5120)) for M in (1, 5, 15, 16)]
+
+
+@pytest.mark.parametrize("M,N,K", _W1_ROWS_SHAPES)
+def test_dec_gemm_single_wave_partial_tile_staging_is_bit_identical(M, N, K):
+    # round 6: a single-wave workgroup stages only the rows of its 16-row activation tile that exist (M < 16: fewer LDS-DMA
+    # instructions; the other rows keep whatever LDS held, and no output depends on them).  SWX_FLAG_DEC_W1_FULL_TILE stages all 16
+    # (rows past M clamped): equal bits for every epilogue of the decode step.  M = 16 is the control where both forms stage the whole
+    # tile; N = 3 K carries the QKV scatter, K = 5120 the K-split residual epilogue.  Every launch must BE the single-wave kernel
+    # (swx_test_dec_plan), or the comparison would be the four-wave kernel against itself.
+    lib = _lib()
+    a, w, cases = _dec_step_cases(np.random.default_rng(M * 7 + N + K), M, N, K)
+    prev = lib.swx_debug_flags(-1)
+    base = prev & ~(_W1_FULL_TILE | 16)
+    try:
+        for name, kw, key in cases:
+            outs = []
+            for flags in (base, base | _W1_FULL_TILE):
+                assert lib.swx_test_dec_plan(M, N, K, kw["epi"], flags) == _DEC_W1, (name, flags)
+                lib.swx_debug_flags(flags)
+                outs.append(_dec_gemm(a, w, **kw))
+            got, ref = outs
             for k in ([key] if key else ["c", "kcache", "vcache"]):
                 assert np.isfinite(got[k]).all() and np.abs(got[k]).max() > 0, (name, k)
                 assert np.array_equal(got[k], ref[k]), (name, k, float(np.abs(got[k] - ref[k]).max()))

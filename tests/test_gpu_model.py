@@ -650,7 +650,7 @@ def test_score_alignment_dtw_strict(name, heads):
 
 @pytest.mark.parametrize("name", ["tiny.en", "base.en"])
 def test_score_f16_small_pass_on_dec_gemms_equals_general_path(name):
-    # teacher-forced pass of ONE window (<= 160 rows) on the decode-step "dec" GEMMs (decoder_forward_dec: LayerNorm folded,
+    # teacher-forced pass of ONE window (<= 160 rows) on the decode-step "dec" GEMMs (decoder_dec's multi-token arm: LayerNorm folded,
     # K / V scattered by the QKV epilogue at pos0 + token index) vs the per-op path (flag 1), both f16, on weights
     # with non-trivial LayerNorm gamma / beta; then both against the f32 oracle.  This is the pass align() runs per window.
     from stable_ts_amd import _lib

@@ -149,3 +149,15 @@ def test_plan_of_the_tall_dec_gemm_cases(lib):
     assert plan(5, 1280, 1280, 4, 0) == DEC_W1 and plan(5, 1280, 1280, 4, 16) == DEC_W4
     assert plan(5, 5120, 1280, 1 | 2, 0) == DEC_W1 and plan(100, 5120, 1280, 1 | 2, 0) == DEC_W4
     assert plan(5, 1000, 1280, 4, 0) < 0 and plan(5, 1280, 1000, 4, 0) < 0
+
+
+def test_plan_of_the_single_wave_row_staging_cases(lib):
+    # test_dec_gemm_single_wave_partial_tile_staging_is_bit_identical (tests/test_gpu_kernels.py): every launch of it is the single-wave
+    # kernel, with the row-staging switch (1024) off and on; the switch is not the multi-token self-attention's (256) any more
+    plan = lib.swx_test_dec_plan
+    for N, K in ((384, 384), (1280, 1280), (3840, 1280), (1280, 5120)):
+        epis = [4 | 16] + ([1, 1 | 2] if K <= 1280 else []) + ([1 | 8] if N == 3 * K else [])
+        for M in (1, 5, 15, 16):
+            for epi in epis:
+                assert plan(M, N, K, epi, 0) == DEC_W1 and plan(M, N, K, epi, 1024) == DEC_W1, (M, N, K, epi)
+                assert plan(M, N, K, epi, 16) == DEC_W4, (M, N, K, epi)
