@@ -333,6 +333,28 @@ size_t swx_loudness_probe_scratch_bytes(int W);
 int swx_pcm_edit(const float *d_clean, float *d_probe, int64_t stride, int n_rows, const int32_t *d_ops,
                  const int32_t *d_row_start, int n_ops, void *stream);
 
+/* ---- denoiser="noisereduce": non-stationary spectral gating of PCM on the device (csrc/swx_denoise.hip; the reference hands the
+ * audio to the noisereduce package, stable_whisper/audio/noisereduce.py:38-87).  The statement that is implemented -- STFT with a
+ * periodic Hann window, a moving mean of |X| over n_mean frames, a sigmoid mask, a triangular smoothing of the mask over
+ * (2 n_grad_freq + 1) x (2 n_grad_time + 1) bins, inverse STFT, NaN -> 0 and +-inf -> +-FLT_MAX -- is written out in DESIGN.md
+ * section 8.  d_pcm f32 [rows] rows pcm_stride samples apart, n >= 1 samples each, independent signals (the channels of a
+ * recording); d_out f32 the same shape, out_stride apart, must not overlap d_pcm.  Arithmetic is f32; the output is the same bits
+ * for every block size, row count and run.  d_scratch: swx_spectral_gate_scratch_bytes(rows, cfg) bytes, 16-byte aligned; the size
+ * does not depend on n (the recording is walked in blocks of frames).  No model handle, no allocation, no host synchronisation,
+ * every launch on `stream`.  A bad argument (a cfg outside the ranges below, too little scratch, overlapping buffers) returns
+ * "invalid argument" before any launch. */
+typedef struct swx_gate_cfg {
+    int32_t n_fft;          /* 256, 512 or 1024; hop = n_fft / 4, window = n_fft */
+    int32_t n_mean;         /* M >= 1: frames of the moving mean, (M - 1) / 2 of them before the frame */
+    float   thresh, slope, prop_decrease;
+    int32_t n_grad_freq, n_grad_time;   /* 1 .. 128 each; both 0 = no smoothing */
+} swx_gate_cfg;
+size_t swx_spectral_gate_scratch_bytes(int rows, const swx_gate_cfg *cfg);   /* 0 for a bad argument */
+int swx_spectral_gate(const float *d_pcm, int64_t pcm_stride, int rows, int64_t n, const swx_gate_cfg *cfg, float *d_out,
+                      int64_t out_stride, void *d_scratch, size_t scratch_bytes, void *stream);
+/* tests only: output hops per block of the walk (0 = the default); changes swx_spectral_gate_scratch_bytes, never the output */
+int swx_test_spectral_gate_block(int frames_per_block);
+
 /* ---- f2 audio front-end: FLAC decoding on the HOST (no device work; csrc/swx_flac.hip).  The reference pipes every container
  * through an `ffmpeg -f s16le` child process (stable_whisper/audio/utils.py:63-125); offline boxes have no ffmpeg and the
  * reference's only real-speech fixture is test/jfk.flac, so native FLAC streams are decoded here: STREAMINFO + frames with

@@ -25,6 +25,11 @@ class swx_flac_info(Structure):
                 ("max_block", c_int32), ("total_samples", c_int64), ("md5", ctypes.c_uint8 * 16)]
 
 
+class swx_gate_cfg(Structure):
+    _fields_ = [("n_fft", c_int32), ("n_mean", c_int32), ("thresh", c_float), ("slope", c_float), ("prop_decrease", c_float),
+                ("n_grad_freq", c_int32), ("n_grad_time", c_int32)]
+
+
 class swx_decode_cfg(Structure):
     _fields_ = [
         ("n_windows", c_int32), ("n_group", c_int32), ("beam", c_int32), ("temperature", c_float),
@@ -99,6 +104,10 @@ SYMBOLS = {
     "swx_loudness_probe": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "swx_loudness_probe_scratch_bytes": (c_size_t, [c_int]),
     "swx_pcm_edit": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "swx_spectral_gate_scratch_bytes": (c_size_t, [c_int, POINTER(swx_gate_cfg)]),
+    "swx_spectral_gate": (c_int, [c_void_p, c_int64, c_int, c_int64, POINTER(swx_gate_cfg), c_void_p, c_int64, c_void_p, c_size_t,
+                                  c_void_p]),
+    "swx_test_spectral_gate_block": (c_int, [c_int]),
     "swx_flac_probe": (c_int, [c_void_p, c_size_t, POINTER(swx_flac_info)]),
     "swx_flac_decode": (c_int64, [c_void_p, c_size_t, c_void_p, c_int64, POINTER(swx_flac_info)]),
     "swx_dtw_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -147,10 +147,11 @@ class Aligner:
                  progress_callback: Optional[Callable] = None, **unsupported):
         if failure_threshold is not None and not 0 <= failure_threshold <= 1:
             raise ValueError(f"``failure_threshold`` ({failure_threshold}) must be between 0 and 1.")
-        for k in ("vad", "denoiser", "only_voice_freq", "stream"):
+        for k in ("vad", "only_voice_freq", "stream"):
             if unsupported.pop(k, None):
                 raise NotImplementedError(f"{k} is outside this package's scope (DESIGN.md section 7)")
-        for k in ("verbose", "vad_threshold", "denoiser_options", "prepend_punctuations", "append_punctuations",
+        for k in ("verbose", "vad_threshold", "denoiser", "denoiser_options",     # (the audio arrives prepared: pop_audio_options)
+                  "prepend_punctuations", "append_punctuations",
                   "dynamic_heads", "aligner", "extra_models", "tokens_per_sec", "all_options"):
             unsupported.pop(k, None)
         if unsupported:

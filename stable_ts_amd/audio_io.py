@@ -19,7 +19,8 @@ Mirrors the part of ``stable_whisper/audio`` the window loop sits on:
   post-prep callback), for in-memory sources and for streamed sources.  ``tests/test_audio_cpu.py`` drives this class
   and the reference's with the same call sequences and compares every returned chunk.
 
-Out of scope: denoisers (demucs / dfnet / noisereduce need their models), yt-dlp URLs.
+``denoiser="noisereduce"`` is the device spectral gate of ``stable_ts_amd/denoise.py``.  Out of scope:
+the denoisers ``demucs`` and ``dfnet`` (they need their model files), yt-dlp URLs.
 """
 import io
 import math
@@ -425,22 +426,41 @@ def audio_to_tensor_resample(audio, original_sample_rate: Optional[int] = None, 
 
 
 def reject_denoiser(denoiser, demucs=None):
-    if denoiser or demucs:
-        raise NotImplementedError("denoisers (demucs / dfnet / noisereduce) need their model files -- out of scope "
-                                  "(DESIGN.md section 7)")
+    """``demucs`` and ``dfnet`` are models; ``noisereduce`` is arithmetic (stable_ts_amd/denoise.py) and passes.  Any other name
+    is left to ``denoise.get_denoiser_func``, which raises the reference's sentence."""
+    if demucs or denoiser in ("demucs", "dfnet"):
+        raise NotImplementedError("the denoisers demucs and dfnet need their model files -- out of scope (DESIGN.md section 7); "
+                                  'denoiser="noisereduce" needs none and is supported')
+
+
+def _denoiser_call_options(denoiser_options: Optional[dict], **kwargs) -> dict:
+    """a copy of the options with the call's own arguments on top (the reference's ``update_options(options, True, ...)``)"""
+    out = dict(denoiser_options or {})
+    out.update(kwargs)
+    return out
 
 
 def prep_audio(audio: Union[str, np.ndarray, torch.Tensor, bytes], denoiser: Optional[str] = None,
                denoiser_options: Optional[dict] = None, only_voice_freq: bool = False, only_ffmpeg: bool = False,
                verbose: Optional[bool] = False, sr: Optional[int] = None, demucs=None, demucs_options=None) -> torch.Tensor:
     """Any supported input -> mono waveform tensor (audio/__init__.py:74-149).  Arrays and tensors are taken as already
-    sampled at ``sr`` and are returned as they are (same object, same device) unless ``only_voice_freq``."""
+    sampled at ``sr`` and are returned as they are (same object, same device) unless a denoiser or ``only_voice_freq`` is
+    asked for.  The denoiser runs first, then the voice-band filter."""
+    from .denoise import get_denoiser_func
     reject_denoiser(denoiser, demucs)
     sr = sr or SAMPLE_RATE
+    denoise_func = get_denoiser_func(denoiser or None, "run")
     if isinstance(audio, (str, bytes)):
-        audio = torch.from_numpy(load_audio(audio, sr=sr, verbose=verbose, only_ffmpeg=only_ffmpeg))
-    elif isinstance(audio, np.ndarray):
-        audio = torch.from_numpy(audio)
+        if denoise_func is None:
+            audio = torch.from_numpy(load_audio(audio, sr=sr, verbose=verbose, only_ffmpeg=only_ffmpeg))
+        else:
+            audio = denoise_func(**_denoiser_call_options(denoiser_options, audio=audio, output_sr=sr, verbose=verbose))
+    else:
+        if isinstance(audio, np.ndarray):
+            audio = torch.from_numpy(audio)
+        if denoise_func is not None:
+            audio = denoise_func(**_denoiser_call_options(denoiser_options, audio=audio, input_sr=sr, output_sr=sr,
+                                                          verbose=verbose))
     if only_voice_freq:
         audio = voice_freq_filter(audio.cpu(), sr)
     return audio
@@ -562,6 +582,7 @@ class AudioLoader:
                  demucs=None, demucs_options=None, load_sections: Optional[List[Section]] = None, negate_load: bool = False):
         if stream and not isinstance(source, str):
             raise NotImplementedError(f"``stream=True`` only supported for string ``source`` but got {type(source)}.")
+        from .denoise import get_denoiser_func
         reject_denoiser(denoiser, demucs)
         self.source = source
         self._sr = sr or SAMPLE_RATE
@@ -575,8 +596,11 @@ class AudioLoader:
         self.only_ffmpeg = only_ffmpeg
         self.new_chunk_divisor = new_chunk_divisor
         self._post_prep_callback = post_prep_callback
-        self._denoiser, self._denoiser_options = None, (denoiser_options or {})
+        self._denoiser, self._denoiser_options = (denoiser or None), dict(denoiser_options or {})
         self._final_save_path = save_path
+        self._denoised_save_path = self._denoiser_options.pop("save_path", None)
+        self._denoised_samples_to_save: List[torch.Tensor] = []
+        self._denoise_model = get_denoiser_func(self._denoiser, "load")(True) if self._denoiser else None
         self._only_voice_freq = only_voice_freq
         self._final_samples_to_save: List[torch.Tensor] = []
         meta = get_metadata(source)
@@ -585,6 +609,7 @@ class AudioLoader:
         self._prev_seek: Optional[int] = None
         self._buffered_samples = torch.tensor([])
         self._pcm: Optional[PcmStream] = open_pcm_stream(source, self._sr) if (self._stream and isinstance(source, str)) else None
+        self._setup_denoiser()
         if test_first_chunk and self.next_chunk(0) is None:
             raise RuntimeError(f'FFmpeg failed to read "{source}".' if isinstance(source, str) else "Failed to load audio.")
 
@@ -677,12 +702,39 @@ class AudioLoader:
         return min_chunk
 
     # -- buffer mechanics
+    def _setup_denoiser(self):
+        """audio/__init__.py:443-499 (``_get_prep_func``): the model and the progress flag into the options; a streamed loader
+        saves only the final audio, a whole-file loader collects the denoised audio for ``save_denoised_audio``"""
+        if self._denoiser:
+            self._denoiser_options["model"] = self._denoise_model
+            if "progress" not in self._denoiser_options:
+                self._denoiser_options["progress"] = False if self._stream else (self.verbose is not None)
+        if self._stream:
+            if self._denoised_save_path:
+                if self._final_save_path:
+                    warnings.warn("Both ``save_path`` in AudioLoad and ``denoiser_options`` were specified, "
+                                  "but only the final audio will be saved for ``stream=True`` in either case. "
+                                  "``denoiser_options`` will be prioritized for ``save_path``.", stacklevel=3)
+                else:
+                    self._final_save_path = self._denoised_save_path
+                self._denoised_save_path = None
+        elif self._denoised_save_path:
+            def append_denoised(samples: torch.Tensor, sr=None):
+                self._denoised_samples_to_save.append(samples.cpu())
+
+            self._denoiser_options["save_path"] = append_denoised
+
     def _prep(self, audio) -> torch.Tensor:
         if self._stream:                                    # per block of freshly converted samples
+            from .denoise import get_denoiser_func
             audio = torch.from_numpy(audio)
+            denoise_func = get_denoiser_func(self._denoiser, "run")
+            if denoise_func is not None:
+                audio = denoise_func(**_denoiser_call_options(self._denoiser_options, audio=audio, input_sr=self._sr,
+                                                              output_sr=self._sr, verbose=self.verbose))
             return voice_freq_filter(audio.cpu(), self._sr) if self._only_voice_freq else audio
-        return prep_audio(audio, only_voice_freq=self._only_voice_freq, only_ffmpeg=self.only_ffmpeg,
-                          verbose=self.verbose, sr=self._sr)
+        return prep_audio(audio, denoiser=self._denoiser, denoiser_options=self._denoiser_options,
+                          only_voice_freq=self._only_voice_freq, only_ffmpeg=self.only_ffmpeg, verbose=self.verbose, sr=self._sr)
 
     def _seek_buffered_samples(self, seek: int) -> int:
         """moves the buffer start to ``seek``; returns how many samples must be read and dropped before it"""
@@ -766,6 +818,15 @@ class AudioLoader:
         return True
 
     # -- bookkeeping
+    def save_denoised_audio(self, path: Optional[str] = None):
+        if not self._denoised_samples_to_save:
+            warnings.warn("Failed to save denoised audio. No stored denoised audio samples found.", stacklevel=2)
+            return
+        if not (path or self._denoised_save_path):
+            warnings.warn("Failed to save denoised audio. No specified path to save.", stacklevel=2)
+            return
+        write_wav(path or self._denoised_save_path, torch.cat(self._denoised_samples_to_save), self._sr)
+
     def save_final_audio(self, path: Optional[str] = None):
         if not self._final_samples_to_save:
             warnings.warn("Failed to save final audio. No stored final audio samples found.", stacklevel=2)
@@ -779,6 +840,9 @@ class AudioLoader:
         pcm = getattr(self, "_pcm", None)
         if pcm is not None:
             pcm.close()
+        if getattr(self, "_denoised_save_path", None) and getattr(self, "_denoised_samples_to_save", None):
+            self.save_denoised_audio()
+            self._denoised_samples_to_save = []
         if getattr(self, "_final_save_path", None) and getattr(self, "_final_samples_to_save", None):
             self.save_final_audio()
             self._final_samples_to_save = []
@@ -792,6 +856,11 @@ class AudioLoader:
         if stream and not self._stream:
             warnings.warn("``stream=True`` will have no effect unless specified at AudioLoader initialization.", stacklevel=2)
         reject_denoiser(denoiser)
+        if denoiser and not self._denoiser:
+            warnings.warn("``denoiser`` will have no effect unless specified at AudioLoader initialization.", stacklevel=2)
+        if denoiser_options and denoiser_options != self._denoiser_options:
+            warnings.warn("``denoiser_options`` does not match the ``denoiser_options`` AudioLoader was initialized with.",
+                          stacklevel=2)
         if only_voice_freq and not self._only_voice_freq:
             warnings.warn("``only_voice_freq=True`` will have no effect unless specified at AudioLoader initialization.",
                           stacklevel=2)

@@ -49,7 +49,10 @@ def transcribe_any(inference_func: Callable, audio: Union[str, np.ndarray, torch
                    min_silence_dur: Optional[float] = None, nonspeech_error: float = 0.1, use_word_position: bool = True,
                    only_voice_freq: bool = False, only_ffmpeg: bool = False, force_order: bool = False,
                    check_sorted: bool = True) -> WhisperResult:
+    from .denoise import get_denoiser_func
     reject_denoiser(denoiser, demucs)
+    denoiser, denoiser_options = denoiser or None, dict(denoiser_options or {})
+    get_denoiser_func(denoiser, "run")                       # an unknown name: the reference's sentence
     if vad:
         raise NotImplementedError("vad needs the Silero model (torch.hub, network) -- out of scope offline")
     if audio_type is not None and (audio_type := audio_type.lower()) not in AUDIO_TYPES:
@@ -61,7 +64,7 @@ def transcribe_any(inference_func: Callable, audio: Union[str, np.ndarray, torch
             raise TypeError(f"{type(audio)} is not supported for ``audio``.")
         audio_type = AUDIO_TYPE_BY_CLASS[type(audio)]
     is_array = isinstance(audio, (np.ndarray, torch.Tensor))
-    if input_sr is None and is_array and (only_voice_freq or suppress_silence or model_sr):
+    if input_sr is None and is_array and (denoiser or only_voice_freq or suppress_silence or model_sr):
         raise ValueError("``input_sr`` is required when ``audio`` is a PyTorch tensor or NumPy array.")
     if model_sr is None and isinstance(audio, (str, bytes)) and audio_type in ("torch", "numpy"):
         raise ValueError('``model_sr`` is required when ``audio_type`` is a "pytorch" or "numpy".')
@@ -72,6 +75,9 @@ def transcribe_any(inference_func: Callable, audio: Union[str, np.ndarray, torch
     temp_audio_file = None
 
     if isinstance(audio, AudioLoader):
+        if denoiser and not audio._denoiser:
+            warnings.warn("``denoiser`` will have no affect unless specified at AudioLoader initialization.", stacklevel=2)
+        denoiser = None
         if only_voice_freq and not audio._only_voice_freq:
             warnings.warn("``only_voice_freq=True`` will have no affect unless specified at AudioLoader initialization.", stacklevel=2)
         only_voice_freq = False
@@ -94,6 +100,18 @@ def transcribe_any(inference_func: Callable, audio: Union[str, np.ndarray, torch
             audio_sr = get_samplerate(audio)
             assert audio_sr is not None, "Failed to get samplerate from ``audio``"
         return audio_sr
+
+    if denoiser:                                             # non_whisper/transcribe.py:233-254
+        denoise_model = denoiser_options.pop("model", None)
+        if denoise_model is None:
+            denoise_model = get_denoiser_func(denoiser, "load")(True)
+        denoiser_options.update(audio=torch.from_numpy(audio) if isinstance(audio, np.ndarray) else audio,
+                                input_sr=current_sr(True), model=denoise_model, verbose=verbose)
+        audio = get_denoiser_func(denoiser, "run")(**denoiser_options)
+        audio_sr = denoise_model.samplerate
+        encoded = False
+        if (denoise_output := denoiser_options.get("save_path")) and audio_type == "str":
+            audio = denoise_output
 
     if only_voice_freq:
         if encoded and audio_sr and model_sr:

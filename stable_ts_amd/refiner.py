@@ -124,10 +124,10 @@ class Refiner:
             self.max_segment_seconds = float(max_segment_length[:-1])
         else:
             self.max_segment_seconds = max_segment_length / sample_rate
-        for k in ("denoiser", "only_voice_freq"):
+        for k in ("only_voice_freq",):
             if unsupported.pop(k, None):
                 raise NotImplementedError(f"{k} is outside this package's scope (DESIGN.md section 7)")
-        for k in ("verbose", "denoiser_options", "all_options", "only_ffmpeg"):
+        for k in ("verbose", "denoiser", "denoiser_options", "all_options", "only_ffmpeg"):   # the audio arrives prepared
             unsupported.pop(k, None)
         if unsupported:
             raise TypeError(f"unexpected keyword argument(s): {', '.join(unsupported)}")

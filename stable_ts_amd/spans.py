@@ -76,7 +76,8 @@ def transcribe_spans(model, audio, n_spans: int = 8, *, spans: Optional[List[Tup
     for k in ("batch_size", "clip_timestamps"):
         if kw.get(k):
             raise NotImplementedError(f"{k} does not combine with span-parallel transcription")
-    wave = as_waveform(audio, only_voice_freq=bool(kw.pop("only_voice_freq", False)))
+    wave = as_waveform(audio, only_voice_freq=bool(kw.pop("only_voice_freq", False)), denoiser=kw.pop("denoiser", None),
+                       denoiser_options=kw.pop("denoiser_options", None))     # once, before the spans are planned
     if wave.shape[-1] == 0:
         raise RuntimeError("Failed to load audio.")
     if spans is None:

@@ -13,7 +13,9 @@ Two drivers share one per-batch routine:
     SURVEY.md 8e describes for throughput / sharding; its oracle is "the reference run on each 30-s clip separately".
 With several tracks the sequential driver advances them in lockstep, one window of each per device batch: the spans of one
 recording (spans.py) or different recordings with a language state each and slots that are refilled (many.py).
-Out of scope here: yt-dlp URLs, denoisers, VAD models, resume (non-WAVE containers need ffmpeg on PATH).
+``denoiser="noisereduce"`` (the device spectral gate, denoise.py) reaches the loader as in the reference (:289-311).
+Out of scope here: yt-dlp URLs, the model denoisers (demucs, dfnet), VAD models, resume (non-WAVE
+containers need ffmpeg on PATH).
 """
 import time
 import warnings
@@ -49,28 +51,39 @@ def _phase(name: str, t0: float) -> float:
 _DECODE_KEYS = set(DecodingOptions.__dataclass_fields__)
 
 
-def as_waveform(audio, only_voice_freq: bool = False) -> torch.Tensor:
+def as_waveform(audio, only_voice_freq: bool = False, denoiser: Optional[str] = None,
+                denoiser_options: Optional[dict] = None) -> torch.Tensor:
     """Whole recording as a 1-D f32 tensor (device preserved for tensors): arrays / tensors are taken as 16 kHz already
     (2-D = channels first, down-mixed), paths and file bytes are decoded by ``audio_io.prep_audio``
-    (alignment.py:167-176 and the other whole-file callers of the reference's ``prep_audio``)."""
+    (alignment.py:167-176 and the other whole-file callers of the reference's ``prep_audio``), which also runs the denoiser
+    and the voice-band filter."""
     audioloader_not_supported(audio)
     if isinstance(audio, np.ndarray):
         audio = torch.from_numpy(np.ascontiguousarray(audio))
     if torch.is_tensor(audio):
         audio = audio.float().mean(0) if audio.ndim == 2 else audio.to(torch.float32)
-    return prep_audio(audio, only_voice_freq=only_voice_freq).to(torch.float32)
+    return prep_audio(audio, denoiser=denoiser, denoiser_options=denoiser_options,
+                      only_voice_freq=only_voice_freq).to(torch.float32)
 
 
 def pop_audio_options(options: dict) -> dict:
     """Takes the audio pre-processing options of the reference's whole-file entry points (align / align_words / refine
-    / locate) out of ``options`` and returns the keyword arguments for :func:`as_waveform`.  Denoisers are out of scope
-    (DESIGN.md section 7); ``stream`` has no effect on a recording that is held whole."""
-    for k in ("denoiser", "demucs"):
-        if options.pop(k, None):
-            raise NotImplementedError(f"{k} is outside this package's scope (DESIGN.md section 7)")
-    for k in ("denoiser_options", "demucs_options", "stream", "only_ffmpeg"):
+    / locate) out of ``options`` and returns the keyword arguments for :func:`as_waveform`: ``only_voice_freq``, and
+    ``denoiser`` / ``denoiser_options`` when a denoiser is asked for.  ``denoiser="noisereduce"`` is the device spectral gate
+    (stable_ts_amd/denoise.py); ``demucs`` and ``dfnet`` need model files and are refused.  ``stream``
+    has no effect on a recording that is held whole."""
+    from .audio_io import reject_denoiser
+    from .denoise import get_denoiser_func
+    denoiser, demucs = options.pop("denoiser", None) or None, options.pop("demucs", None)
+    reject_denoiser(denoiser, demucs)
+    get_denoiser_func(denoiser, "run")                       # an unknown name: the reference's sentence
+    denoiser_options = options.pop("denoiser_options", None)
+    for k in ("demucs_options", "stream", "only_ffmpeg"):
         options.pop(k, None)
-    return dict(only_voice_freq=bool(options.pop("only_voice_freq", False)))
+    out = dict(only_voice_freq=bool(options.pop("only_voice_freq", False)))
+    if denoiser:
+        out.update(denoiser=denoiser, denoiser_options=denoiser_options)
+    return out
 
 
 def _xkv_select(model, xkv, idx: Sequence[int]):
