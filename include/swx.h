@@ -421,6 +421,41 @@ int swx_test_layernorm(int dtype, const void *d_x, const float *d_g, const float
 int swx_test_attention(int dtype, const void *d_q, int64_t ldq, const void *d_k, const void *d_v, int64_t ldkv,
                        void *d_o, int64_t ldo, int B, int H, int nq, int nk, int force_kernel, int vt_kp, void *stream);
 
+/* swx_test_gemm with the arguments of the layout epilogues (csrc/swx_kernels.h: GemmArgs).  `epilogue` bits beyond swx_test_gemm's
+ * 1 bias, 2 GELU, 4 residual d_res (row stride ldc), 8 f32 output:
+ *   16  + d_resf[(m % res_mod)][n], f32 [res_mod][N] (the positional embedding behind conv2)
+ *   64  C rows grouped in batch items of vt_s rows: row m at d_c + (m / vt_s) * vt_bs + (m % vt_s) * ldc
+ *   32  C transposed per head: element (m, n) at d_c + (m / vt_s) * vt_bs + n * vt_kp + m % vt_s (n = head * 64 + dim)
+ *   128 f16: columns [0, N/2) as 64 into d_c, columns [N/2, N) as 32 into d_c2 (column counted from N/2); with d_p also the
+ *       fragment-ordered copy of both halves (batch item b at d_p + b * p_bs, per head ceil(vt_s / 32) * 4096 halfs,
+ *       keys [vt_s, p_nkpad) zeroed; p_nkpad = vt_s rounded up to 32, p_vcol0 = N/2)
+ *   256 f16: columns [0, 2N/3) plain into d_c, columns [2N/3, N) as 32 into d_c2; vt_zero_pad: keys [vt_s, vt_kp) of d_c2 zeroed
+ * lda < K is allowed (the convolutions run as GEMMs over overlapping rows).  force_kernel goes to the launcher unchanged.  Returns -1
+ * for a missing argument and -2 / -4 for a combination no kernel implements (nothing is launched): two layout bits at once; 128 / 256
+ * in f32, on the skinny kernel, with a column split that is no multiple of the planned kernel's tile width, or with vt_s, vt_kp, vt_bs
+ * or M no multiple of 4; d_p without 128 or with ldc, vt_bs or p_bs no multiple of 8; vt_zero_pad without 256. */
+int swx_test_gemm_layout(int dtype, const void *d_a, int64_t lda, const void *d_w, int64_t ldw, const float *d_bias, const void *d_res,
+                         const float *d_resf, int res_mod, void *d_c, int64_t ldc, void *d_c2, void *d_p, int64_t p_bs, int p_nkpad,
+                         int p_vcol0, int vt_s, int vt_kp, int64_t vt_bs, int vt_zero_pad, int M, int N, int K, int epilogue,
+                         int force_kernel, void *stream);
+/* the stand-alone packer of the fragment-ordered cross-K/V copy (f16): d_k [B][nk][ldk] rows, d_vt [B][H][64][vt_kp] (zero padded past
+ * nk), d_packed [B][H][per_head]; all three with `batch_stride` elements between batch items.  vt_kp >= nk rounded up to 32. */
+int swx_test_xkv_pack(const void *d_k, const void *d_vt, void *d_packed, int B, int H, int nk, int ldk, int vt_kp, int64_t batch_stride,
+                      void *stream);
+/* swx_test_attention (f16, V transposed: vt_kp > 0) with explicit batch strides k_bs / v_bs (elements), the fragment-ordered copy
+ * d_packed (batch stride k_bs; NULL: the row layout) and, with d_wq != NULL, the query projection inside the launch: q = LN(x) Wq^T + b
+ * from the residual rows d_x [fq_rows][ldx] (window b owns rows b * nq ..), raw weights d_wq f16 [d][d], d = 64 H, folded into d_scratch
+ * (>= d * d * 2 + 8 d + 1 KiB bytes) exactly as swx_test_dec_gemm folds them for its LayerNorm epilogue; d_q is not read then. */
+int swx_test_attention_packed(const void *d_q, int64_t ldq, const void *d_k, const void *d_v, int64_t ldkv, int64_t k_bs, int64_t v_bs,
+                              const void *d_packed, void *d_o, int64_t ldo, int B, int H, int nq, int nk, int vt_kp, int force_kernel,
+                              const void *d_x, int64_t ldx, int fq_rows, const void *d_wq, const float *d_gamma, const float *d_beta,
+                              const float *d_bias, void *d_scratch, size_t scratch_bytes, void *stream);
+/* which form of the decode cross-attention kernel such a launch gets (host-only, no GPU; the function swx_attention itself executes):
+ * family + 16 * QG + 256 * depth, family 0 = not the decode kernel (flash / row-wise), 1 = row-layout K / V^T, 2 = fragment-ordered
+ * copy, 3 = fragment-ordered copy with the fused query projection (fq_k = 64 H); QG = groups of 16 query rows per workgroup (1, 2, 4);
+ * depth = key blocks a wave keeps in flight (1, 2).  < 0: the call is refused. */
+int swx_test_xattn_plan(int B, int H, int nq, int nk, int vt_kp, int has_packed, int has_fq, int force_kernel, int flags);
+
 /* decode-step self-attention (f16): variant 0 = the single-token kernel without long-context code (positions < 128), 1 = the
  * single-token kernel, 2 = the general cached-attention kernel (their bit-identity reference).  d_q [R][d]; caches
  * [R_phys][n_ctx][d] with the new token's K / V already at position pos0[r] of row r; d_anc [R][n_ctx] or NULL; d_o [R][d]. */

@@ -151,6 +151,14 @@ SYMBOLS = {
     "swx_test_layernorm": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "swx_test_attention": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int,
                                    c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "swx_test_gemm_layout": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                     c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_int,
+                                     c_int, c_int, c_int, c_void_p]),
+    "swx_test_xkv_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
+    "swx_test_attention_packed": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                          c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_int, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "swx_test_xattn_plan": (c_int, [c_int] * 9),
 }
 
 _lib = None

@@ -1636,6 +1636,40 @@ static bool f32_flash_ready(bool vt, bool split)
     return state[dev][v] > 0;
 }
 
+SwxXattnPlan swx_xattn_plan(int dtype, const AttnArgs &a, int force_kernel, int flags)
+{
+    SwxXattnPlan p{SWX_XA_NOT_DECODE, 1, 1};
+    // the decode kernel also takes a SMALL multi-row pass (align(): one window of ~100 rows) as groups of 16 rows, when the
+    // fragment-ordered K / V^T copy exists and the flash grid would be tiny
+    const int ngrp = cdiv(a.nq, 16);
+    const bool by_batch = flags & SWX_FLAG_SCORE_TILED;       // round 3's size-dependent choice (A/B only)
+    const bool small_pass = a.nq > 16 && a.kv_packed && !(flags & SWX_FLAG_NO_PACKED_XKV) && force_kernel == 0 &&
+                            (!by_batch || (a.nq <= 160 && (int64_t)a.B * a.H * ngrp <= 1024));
+    const bool dec = (dtype == SWX_F16) && a.vt_kp > 0 && (a.nq <= 16 || small_pass) && a.nk >= 128 && (force_kernel == 3 || force_kernel == 0);
+    if (force_kernel == 3 && !dec) { p.family = -5; return p; }
+    if (!dec) return p;
+    // groups of 16 query rows per workgroup: one while the launch is small (a decode step; align(): one window = 100-160
+    // workgroups), up to four when many windows share the pass (the head's K / V^T is then streamed once per 64 rows)
+    const int64_t wgs1 = (int64_t)a.B * a.H * ngrp;
+    p.qg = (a.nq <= 16 || wgs1 <= 512) ? 1 : (ngrp >= 4 && wgs1 > 2048) ? 4 : 2;
+    const bool packed = a.kv_packed && !(flags & SWX_FLAG_NO_PACKED_XKV);     // else row-layout K / V^T: the reference
+    const bool r5_loop = (flags & SWX_FLAG_XATTN_R5) != 0;                    // one key block per wave in flight (A/B)
+    if (packed && a.fq_w && p.qg == 1 && a.nq <= 16) {
+        const int fq = a.fq_k / 32;
+        const bool offered = a.fq_k % 32 == 0 && (fq == 12 || fq == 16 || fq == 20 || fq == 24 || fq == 32 || fq == 40);
+        p.family = offered ? SWX_XA_PACKED_FQ : -5;
+        p.depth = r5_loop ? 1 : 2;
+    } else if (a.fq_w) {
+        p.family = -5;                  // the fused query projection exists on the packed single-group kernel only
+    } else if (packed) {
+        p.family = SWX_XA_PACKED;
+        p.depth = r5_loop ? 1 : 2;
+    } else {
+        p.family = SWX_XA_ROW;          // attn_decode_cross_f16<false, QG>: one key block per wave in flight
+    }
+    return p;
+}
+
 int swx_attention(int dtype, const AttnArgs &a_in, int force_kernel, hipStream_t s)
 {
     const AttnArgs &a = a_in;
@@ -1643,25 +1677,17 @@ int swx_attention(int dtype, const AttnArgs &a_in, int force_kernel, hipStream_t
     if (a.nk > RW_MAXK) return -5;
     const bool flash = (dtype == SWX_F16) && (force_kernel == 2 || (force_kernel >= 4 && force_kernel <= 6) || (force_kernel == 0 && a.nq >= 32));
     const size_t esz = dtype == SWX_F16 ? 2 : 4;
-    // the decode kernel also takes a SMALL multi-row pass (align(): one window of ~100 rows) as groups of 16 rows, when the
-    // fragment-ordered K / V^T copy exists and the flash grid would be tiny
-    const int ngrp = cdiv(a.nq, 16);
-    const bool by_batch = swx_flags() & SWX_FLAG_SCORE_TILED;       // round 3's size-dependent choice (A/B only)
-    const bool small_pass = a.nq > 16 && a.kv_packed && !(swx_flags() & SWX_FLAG_NO_PACKED_XKV) && force_kernel == 0 &&
-                            (!by_batch || (a.nq <= 160 && (int64_t)a.B * a.H * ngrp <= 1024));
-    const bool dec = (dtype == SWX_F16) && a.vt_kp > 0 && (a.nq <= 16 || small_pass) && a.nk >= 128 && (force_kernel == 3 || force_kernel == 0);
-    if (force_kernel == 3 && !dec) return -5;
+    const SwxXattnPlan xp = swx_xattn_plan(dtype, a, force_kernel, swx_flags());
+    if (xp.family < 0) return xp.family;
+    const bool dec = xp.family != SWX_XA_NOT_DECODE;
     if (dec) {
         SwxProfScope prof(PC_ATTN_ROWWISE, (double)a.B * a.H * 64 * esz * (2.0 * a.nk + 2.0 * a.nq) +
                                                (a.fq_w ? 2.0 * a.H * 64 * a.fq_k + 2.0 * a.fq_rows * a.fq_k : 0.0), s);
-        // groups of 16 query rows per workgroup: one while the launch is small (a decode step; align(): one window = 100-160
-        // workgroups), up to four when many windows share the pass (the head's K / V^T is then streamed once per 64 rows)
-        const int64_t wgs1 = (int64_t)a.B * a.H * ngrp;
-        const int qg = (a.nq <= 16 || wgs1 <= 512) ? 1 : (ngrp >= 4 && wgs1 > 2048) ? 4 : 2;
+        const int ngrp = cdiv(a.nq, 16), qg = xp.qg;
         dim3 gd(a.H, a.B, cdiv(ngrp, qg));
-        const bool packed = a.kv_packed && !(swx_flags() & SWX_FLAG_NO_PACKED_XKV);     // else row-layout K / V^T: the reference
-        const bool r5_loop = (swx_flags() & SWX_FLAG_XATTN_R5) != 0;                    // one key block per wave in flight (A/B)
-        if (packed && a.fq_w && qg == 1 && a.nq <= 16) {
+        const bool packed = xp.family == SWX_XA_PACKED;
+        const bool r5_loop = xp.depth == 1;                    // one key block per wave in flight (A/B: SWX_FLAG_XATTN_R5)
+        if (xp.family == SWX_XA_PACKED_FQ) {
             // fused query projection: + [16][K] residual tile, statistics, q tile in dynamic LDS
             AttnArgs a = a_in;
             a.fq_full_tile = (swx_flags() & SWX_FLAG_XQ_FULL_TILE) ? 1 : 0;
@@ -1690,7 +1716,6 @@ int swx_attention(int dtype, const AttnArgs &a_in, int force_kernel, hipStream_t
             }
 #undef SWX_XQ
         } else if (packed) {
-            if (a.fq_w) return -5;
             if (r5_loop) {
                 if (qg == 1) hipLaunchKernelGGL((attn_decode_cross_f16<true, 1>), gd, dim3(256), 0, s, a);
                 else if (qg == 2) hipLaunchKernelGGL((attn_decode_cross_f16<true, 2>), gd, dim3(256), 0, s, a);
@@ -1700,8 +1725,7 @@ int swx_attention(int dtype, const AttnArgs &a_in, int force_kernel, hipStream_t
                 else if (qg == 2) hipLaunchKernelGGL((attn_decode_cross2_f16<true, 2>), gd, dim3(256), 0, s, a);
                 else hipLaunchKernelGGL((attn_decode_cross2_f16<true, 4>), gd, dim3(256), 0, s, a);
             }
-        } else {
-            if (a.fq_w) return -5;
+        } else {      // SWX_XA_ROW
             if (qg == 1) hipLaunchKernelGGL((attn_decode_cross_f16<false, 1>), gd, dim3(256), 0, s, a);
             else if (qg == 2) hipLaunchKernelGGL((attn_decode_cross_f16<false, 2>), gd, dim3(256), 0, s, a);
             else hipLaunchKernelGGL((attn_decode_cross_f16<false, 4>), gd, dim3(256), 0, s, a);

@@ -251,6 +251,15 @@ int swx_xkv_pack(const void *k, const void *vt, void *packed, int B, int H, int 
 #define SWX_VT_KP 1536               // padded key count of the transposed cross-attention V (64-key tiles never run off a row)
 // dense (non-causal) attention over nk keys: encoder self-attention and cross-attention
 int swx_attention(int dtype, const AttnArgs &a, int force_kernel, hipStream_t s);
+// whether swx_attention runs a launch on the decode cross-attention kernel, and on which form of it (pure: the function the launcher
+// itself executes; swx_test_xattn_plan).  Reads the scalar fields of `a` and whether a.kv_packed / a.fq_w are set, no memory.
+// `flags`: swx_debug_flags.  family < 0: the error swx_attention returns.
+enum SwxXattnFamily { SWX_XA_NOT_DECODE = 0,     // flash / f32 / row-wise kernels
+                      SWX_XA_ROW = 1,            // attn_decode_cross_f16<false, QG>: row-layout K / V^T
+                      SWX_XA_PACKED = 2,         // attn_decode_cross2_f16<true, QG> (depth 2) / attn_decode_cross_f16<true, QG> (depth 1)
+                      SWX_XA_PACKED_FQ = 3 };    // attn_decode_cross_xq2_f16<FQ> (depth 2) / attn_decode_cross_xq_f16<FQ> (depth 1)
+struct SwxXattnPlan { int family, qg, depth; };  // qg: groups of 16 query rows per workgroup; depth: key blocks of a wave in flight
+SwxXattnPlan swx_xattn_plan(int dtype, const AttnArgs &a, int force_kernel, int flags);
 // V [B][n][ldv] -> per-head transposed V^T [B][H][64][kp] (keys contiguous, zero padded): feeds the MFMA flash kernel's vector path
 int swx_transpose_v(const void *v, int64_t ldv, int64_t v_bs, int n, void *vt, int kp, int64_t vt_bs, int B, int H, hipStream_t s);
 int swx_pad_zero(void *base, int64_t row_bytes, int64_t batch_bytes, int off_bytes, int pad_bytes, int rows, int nb, hipStream_t s);

@@ -2293,6 +2293,101 @@ int swx_test_attention(int dtype, const void *d_q, int64_t ldq, const void *d_k,
     return swx_attention(dtype, a, force_kernel, S(stream));
 }
 
+// swx_test_gemm with every field of GemmArgs the layout epilogues read.  A combination the kernels do not implement is refused here
+// (-2) instead of launched: the column split of EPI_KV / EPI_QKV_VT has to fall on a tile boundary of the kernel the plan picks, both
+// are f16 tiled-kernel epilogues, and the fragment-ordered copy is written by EPI_KV's fast paths only.
+int swx_test_gemm_layout(int dtype, const void *d_a, int64_t lda, const void *d_w, int64_t ldw, const float *d_bias, const void *d_res,
+                         const float *d_resf, int res_mod, void *d_c, int64_t ldc, void *d_c2, void *d_p, int64_t p_bs, int p_nkpad,
+                         int p_vcol0, int vt_s, int vt_kp, int64_t vt_bs, int vt_zero_pad, int M, int N, int K, int epilogue,
+                         int force_kernel, void *stream)
+{
+    if (dtype != SWX_F16 && dtype != SWX_F32) return -1;
+    if (!d_a || !d_w || !d_c || M <= 0 || N <= 0 || K <= 0 || lda <= 0 || ldw < K) return -1;
+    if ((epilogue & EPI_BIAS) && !d_bias) return -1;
+    if ((epilogue & EPI_RES) && !d_res) return -1;
+    if ((epilogue & EPI_RESF32MOD) && (!d_resf || res_mod <= 0)) return -1;
+    const int layout = epilogue & (EPI_CBATCH | EPI_STORE_VT | EPI_KV | EPI_QKV_VT);
+    if (layout && vt_s <= 0) return -1;
+    if ((epilogue & (EPI_STORE_VT | EPI_KV | EPI_QKV_VT)) && vt_kp < vt_s) return -1;
+    if (layout & (layout - 1)) return -2;                       // one layout epilogue per launch
+    if (epilogue & (EPI_KV | EPI_QKV_VT)) {
+        if (dtype != SWX_F16 || !d_c2) return -2;
+        if ((epilogue & EPI_KV) ? N % 2 != 0 : N % 3 != 0) return -2;
+        const int split = (epilogue & EPI_KV) ? N / 2 : (N / 3) * 2;
+        const bool ptr16 = (uintptr_t)d_a % 16 == 0 && (uintptr_t)d_w % 16 == 0;
+        const int plan = swx_gemm_plan_f16(M, N, K, epilogue, 1, 1, ptr16, force_kernel, swx_flags());
+        if (plan < 0) return plan;
+        if (plan == SWX_GEMM_SKINNY || plan == SWX_GEMM_BIG) return -2;
+        const int width = (plan == SWX_GEMM_GLDS64 || plan == SWX_GEMM_RING64) ? 64 : 128;
+        if (split % width != 0) return -2;
+        // the transposed half and the key padding are written by the 4-row column-wise path only
+        if (vt_s % 4 != 0 || vt_kp % 4 != 0 || vt_bs % 4 != 0 || M % 4 != 0) return -2;
+    } else if (vt_zero_pad) return -2;
+    if (d_p) {
+        // ... and the copy's K pieces by the 16-byte row path only
+        if (!(epilogue & EPI_KV) || ldc % 8 != 0 || vt_bs % 8 != 0 || p_bs % 8 != 0 || p_vcol0 != N / 2) return -2;
+        if (p_nkpad != ((vt_s + 31) / 32) * 32 || (epilogue & (EPI_RES | EPI_GELU | EPI_OUT_F32 | EPI_RESF32MOD))) return -2;
+    }
+    GemmArgs g = gemm_args(d_a, lda, d_w, ldw, d_bias, d_c, ldc, M, N, K, epilogue);
+    g.R = d_res; g.ldr = ldc; g.Rf = d_resf; g.res_mod = res_mod > 0 ? res_mod : 1;
+    g.C2 = d_c2; g.P = d_p; g.p_bs = p_bs; g.p_nkpad = p_nkpad; g.p_vcol0 = p_vcol0;
+    g.vt_s = vt_s; g.vt_kp = vt_kp; g.vt_bs = vt_bs; g.vt_zero_pad = vt_zero_pad ? 1 : 0;
+    return swx_gemm(dtype, g, force_kernel, S(stream));
+}
+
+int swx_test_xkv_pack(const void *d_k, const void *d_vt, void *d_packed, int B, int H, int nk, int ldk, int vt_kp, int64_t batch_stride,
+                      void *stream)
+{
+    if (!d_k || !d_vt || !d_packed || B <= 0 || H <= 0 || nk <= 0) return -1;
+    if (ldk < 64 * H || ldk % 8 != 0 || vt_kp % 8 != 0 || batch_stride % 8 != 0) return -2;
+    return swx_xkv_pack(d_k, d_vt, d_packed, B, H, nk, ldk, vt_kp, batch_stride, S(stream));
+}
+
+// swx_test_attention (f16, transposed V) with the batch strides, the fragment-ordered copy and the fused query projection as arguments.
+// d_wq != null: q = LN(x) Wq^T + b inside the launch -- the raw weights [d][d] (d = 64 H) are folded into d_scratch (d * d halfs +
+// 2 d floats, 256-byte aligned pieces) as swx_test_dec_gemm_kl folds them for DEC_LN; d_q is not read; no prefetch target.
+int swx_test_attention_packed(const void *d_q, int64_t ldq, const void *d_k, const void *d_v, int64_t ldkv, int64_t k_bs, int64_t v_bs,
+                              const void *d_packed, void *d_o, int64_t ldo, int B, int H, int nq, int nk, int vt_kp, int force_kernel,
+                              const void *d_x, int64_t ldx, int fq_rows, const void *d_wq, const float *d_gamma, const float *d_beta,
+                              const float *d_bias, void *d_scratch, size_t scratch_bytes, void *stream)
+{
+    if (!d_o || B <= 0 || H <= 0 || nq <= 0 || nk <= 0 || vt_kp <= 0) return -1;
+    if (!d_packed && (!d_k || !d_v)) return -1;
+    if (!d_wq && !d_q) return -1;
+    if (vt_kp % 8 != 0 || vt_kp < ((nk + 31) / 32) * 32 || k_bs % 8 != 0 || v_bs % 8 != 0 || ldo < 64 * H) return -2;
+    if (d_k && (ldkv < 64 * H || ldkv % 8 != 0)) return -2;
+    hipStream_t s = S(stream);
+    AttnArgs a{};
+    a.q = d_q; a.ldq = ldq; a.k = d_k; a.v = d_v; a.ldkv = ldkv; a.o = d_o; a.ldo = ldo;
+    a.k_bs = k_bs; a.v_bs = v_bs; a.vt_kp = vt_kp; a.kv_packed = d_packed;
+    a.B = B; a.H = H; a.nq = nq; a.nk = nk; a.q_rows_per_batch = nq;
+    if (d_wq) {
+        const int d = 64 * H;
+        if (!d_x || !d_gamma || !d_beta || !d_bias || !d_scratch) return -1;
+        if (ldx < d || ldx % 8 != 0 || fq_rows < (B - 1) * nq + 1) return -2;
+        if (scratch_bytes < align_up((size_t)d * d * 2) + 2 * align_up((size_t)d * 4)) return -8;
+        unsigned char *p = (unsigned char *)d_scratch;
+        f16 *wf = (f16 *)p; p += align_up((size_t)d * d * 2);
+        float *c1 = (float *)p; p += align_up((size_t)d * 4);
+        float *c2 = (float *)p;
+        SWX_TRY(swx_fold_ln(d_wq, d_gamma, d_beta, d_bias, wf, c1, c2, d, d, s));
+        a.fq_x = (const f16 *)d_x; a.fq_ldx = ldx; a.fq_rows = fq_rows; a.fq_w = wf; a.fq_c1 = c1; a.fq_c2 = c2; a.fq_k = d;
+    } else if (ldq < 64 * H || ldq % 8 != 0) return -2;
+    return swx_attention(SWX_F16, a, force_kernel, s);
+}
+
+int swx_test_xattn_plan(int B, int H, int nq, int nk, int vt_kp, int has_packed, int has_fq, int force_kernel, int flags)
+{
+    static const _Float16 some_memory[1] = {};   // only whether a.kv_packed / a.fq_w are set matters to the plan
+    if (B <= 0 || H <= 0 || nq <= 0 || nk <= 0) return -1;
+    AttnArgs a{};
+    a.B = B; a.H = H; a.nq = nq; a.nk = nk; a.vt_kp = vt_kp; a.q_rows_per_batch = nq;
+    a.kv_packed = has_packed ? some_memory : nullptr;
+    if (has_fq) { a.fq_w = some_memory; a.fq_k = 64 * H; }
+    const SwxXattnPlan p = swx_xattn_plan(SWX_F16, a, force_kernel, flags);
+    return p.family < 0 ? p.family : p.family + 16 * p.qg + 256 * p.depth;
+}
+
 int swx_test_lane_xor(const uint32_t *d_in, uint32_t *d_out, int n_waves, void *stream)
 {
     if (!d_in || !d_out || n_waves <= 0) return -1;
