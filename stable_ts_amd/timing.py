@@ -2,7 +2,7 @@
 
 Mirrors stable_whisper/timing.py (find_alignment_stable :202-306, split_word_tokens :344-392,
 add_word_timestamps_stable :411-500).  The teacher-forced decoder pass, the head selection / softmax / z-norm /
-median filter / head-mean and the DTW all run on the GPU (csrc/swx_runtime.hip::swx_score, swx_align.hip,
+median filter / head-mean and the DTW all run on the GPU (csrc/swx_score.hip::swx_score, swx_align.hip,
 swx_dtw.hip); what stays here is the token<->word bookkeeping, which is string work.
 
 The default ('legacy') aligner with the model's alignment heads is one fused device call (``swx_score``).  The

@@ -6,7 +6,7 @@ reference (``run_reference``) does not restate a rule: it drives the oracle's ow
 -- in the order and with the two extra lines (ts mask, ``nan_to_num_``) of ``oracle.stable.DecodingTaskStable._main_loop``, one
 window at a time as upstream decodes.  Two expectations have no upstream counterpart and are restated here from the host code
 they check, so those two comparisons are not independent of it: the number of steps executed (the loop of ``run_reference``
-follows decode_loop_stop in csrc/swx_runtime.hip on the steps at which the reference's windows ended) and ``pos0`` (the last
+follows decode_loop_stop in csrc/swx_decjob.hip on the steps at which the reference's windows ended) and ``pos0`` (the last
 position a window wrote, held below n_ctx).  While it runs it MEASURES, in float64, the margin of every decision (so that the f32
 arithmetic of the kernels cannot legitimately flip one) and counts which rule branches the case list reaches.
 
@@ -392,7 +392,7 @@ def run_reference(case) -> Ref:
             counts["unused_slot"] += 1
         if r["done"] == "ctx_full":
             counts["ctx_full_ragged" if ragged else "ctx_full_uniform"] += 1
-    # the host loop's exits (swx_runtime.hip: decode_loop_stop) on the steps at which the windows ended
+    # the host loop's exits (swx_decjob.hip: decode_loop_stop) on the steps at which the windows ended
     end = [r["last"] if r["done"] != "budget" else None for r in wins]
     steps = 0
     for i in range(case.sample_len):

@@ -342,3 +342,67 @@ def test_word_means_equal_numpy_mean_per_word_bit_for_bit():
         for a, b in zip(ref, got):
             assert type(a) is type(b) and (a == b or (np.isnan(a) and np.isnan(b))), (cnts, a, b)
 
+
+
+# Byte totals of the two decode-state layouts, taken from a build of the commit BEFORE the layouts were unified
+# (swx_decode_state_layout, csrc/swx_model.h): the workspace of a model handle and the scratch of swx_test_decode_script.
+# Key: (model, dtype (0 f32 / 1 f16), max_windows, max_rows) and (W, G, n_vocab, n_ctx).
+_WORKSPACE_BYTES = {
+    ("tiny.en", 0, 1, 1): 82877952,
+    ("tiny.en", 0, 1, 5): 104927232,
+    ("tiny.en", 0, 20, 100): 1860691968,
+    ("tiny.en", 0, 3, 48): 469991168,
+    ("tiny.en", 1, 1, 1): 65033984,
+    ("tiny.en", 1, 1, 5): 76073216,
+    ("tiny.en", 1, 20, 100): 1283609088,
+    ("tiny.en", 1, 3, 48): 292595968,
+    ("large-v3", 0, 1, 1): 1131696640,
+    ("large-v3", 0, 1, 5): 1718928384,
+    ("large-v3", 0, 20, 100): 34140669696,
+    ("large-v3", 0, 3, 48): 9974745344,
+    ("large-v3", 1, 1, 1): 1009143808,
+    ("large-v3", 1, 1, 5): 1302774272,
+    ("large-v3", 1, 20, 100): 25817587456,
+    ("large-v3", 1, 3, 48): 6304072448,
+}
+_SCRIPT_WS_BYTES = {
+    (1, 1, 51865, 448): 276224,
+    (1, 1, 51865, 16): 214272,
+    (1, 1, 97, 448): 69120,
+    (1, 1, 97, 16): 7168,
+    (3, 5, 51865, 448): 3397888,
+    (3, 5, 51865, 16): 3128064,
+    (3, 5, 97, 448): 291840,
+    (3, 5, 97, 16): 22016,
+    (2, 16, 51865, 448): 6991104,
+    (2, 16, 51865, 16): 6659328,
+    (2, 16, 97, 448): 364800,
+    (2, 16, 97, 16): 33024,
+}
+
+
+def test_decode_state_layouts_keep_their_sizes():
+    """The workspace layout and the scripted-decode scratch share one list of decode-state regions; their totals are pinned to the
+    bytes they had as two hand-written lists.  swx_model_create touches no device, so this runs without one."""
+    import ctypes
+
+    import stable_ts_amd as sw
+    from stable_ts_amd import _lib
+    lib = _lib.load(build_if_missing=True)
+    handles = {}
+    try:
+        for (name, dtype, w, r), want in _WORKSPACE_BYTES.items():
+            if (name, dtype) not in handles:
+                d = sw.dims_for(name)
+                cd = _lib.swx_dims(**{f: getattr(d, f) for f, _ in _lib.swx_dims._fields_})
+                h = ctypes.c_void_p()
+                assert lib.swx_model_create(ctypes.byref(cd), dtype, ctypes.byref(h)) == 0
+                handles[(name, dtype)] = h
+            assert lib.swx_workspace_bytes(handles[(name, dtype)], w, r) == want, (name, dtype, w, r)
+    finally:
+        for h in handles.values():
+            lib.swx_model_destroy(h)
+    for (W, G, V, n_ctx), want in _SCRIPT_WS_BYTES.items():
+        cfg = _lib.swx_decode_cfg()
+        cfg.n_windows, cfg.n_group, cfg.sample_len = W, G, 8
+        assert lib.swx_test_decode_script_ws_bytes(ctypes.byref(cfg), V, n_ctx) == want, (W, G, V, n_ctx)

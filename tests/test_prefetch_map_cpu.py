@@ -51,7 +51,7 @@ DIMS = {"tiny": 384, "base": 512, "small": 768, "medium": 1024, "large": 1280}
 
 
 def chain(d):
-    """decoder_dec (swx_runtime.hip): issuer (N, K, K-split allowed) -> the projection it prefetches"""
+    """decoder_dec (swx_decoder.hip): issuer (N, K, K-split allowed) -> the projection it prefetches"""
     return [((3 * d, d, False), (d, d)), ((d, d, False), (d, d)), ((d, d, False), (d, d)), ((d, d, False), (4 * d, d)),
             ((4 * d, d, False), (d, 4 * d)), ((d, 4 * d, True), (3 * d, d))]
 
