@@ -130,7 +130,10 @@ typedef struct swx_decode_cfg {
                                      filtered logits / T, i.e. a Categorical(logits / T) sample like upstream's GreedyDecoder,
                                      but NOT the reference's (framework Philox) random stream: a T > 0 retry is reproducible for a given (seed, uid)
                                      whatever the batch it is decoded in, and is not token-identical with the reference's.
-                                     NULL: the window's index in this job is its uid. */
+                                     The variate by the top 24 bits k of the 32-bit hash word: u_k = (k + 0.5) * 2^-24, added
+                                     to logits / T is -ln(-ln u_k) -- finite for every word (f32 holds u below 1 in the top
+                                     bucket), so a masked id is never drawn.  The hash keys a row on uid * 0x9E3779B1 + slot.
+                                     NULL: the row's index in this job is its key. */
     const float *noise;           /* DEVICE array [sample_len][W * G][n_vocab] f32 or NULL.  Non-NULL (greedy decoder, temperature > 0):
                                      the draw of row r at step t is argmax_i(logits[i] / T - log(noise[t][r][i])): upstream's
                                      Categorical(logits / T).sample() is a multinomial draw of one sample, which the framework
@@ -549,8 +552,8 @@ int swx_test_gelu_pair(uint64_t *d_out, void *stream);
  * d_prefill_logits, then per step [copy the step's slice of the script into the logits rows -> selection of token i] launched
  * eagerly, and finalize.  The loop ends by the conditions of swx_decode (one shared host function): context full, every window
  * done (polled every 8 steps once min_tokens have been sampled), sample_len used up.  n_vocab and n_ctx are free (the token
- * buffers are n_ctx + 1 wide); cfg is read as by swx_decode (sample_begins: a ragged job; sot_index / sot_indices / window_uid are
- * not used; noise: DEVICE [sample_len][W * G][n_vocab]); debug flag 8192 selects the memory-walking kernel as in swx_decode.
+ * buffers are n_ctx + 1 wide); cfg is read as by swx_decode (sample_begins: a ragged job; window_uid: HOST [W], keys the built-in
+ * draw as there, NULL = row index; sot_index / sot_indices are not used; noise: DEVICE [sample_len][W * G][n_vocab]); debug flag 8192 selects the memory-walking kernel as in swx_decode.
  *  d_init_tokens int32 [W][longest window]; d_suppress int32 [n_suppress] or NULL; d_ts_mask uint8 [W][1501] or NULL
  *  d_prefill_logits f32 [W][2][n_vocab]  row 0: the SOT position (no-speech probability), row 1: the logits token 0 is selected from
  *  d_script f32 [n_script][W * G][n_vocab]  slice i - 1: the logits token i is selected from ("size out of range" when the loop
@@ -563,6 +566,13 @@ int swx_test_decode_script(const swx_decode_cfg *cfg, int n_vocab, int n_ctx, co
                            const int32_t *d_suppress, const uint8_t *d_ts_mask, const float *d_prefill_logits,
                            const float *d_script, int n_script, int32_t *d_tokens_out, int32_t *d_lens_out, float *d_sumlp_out,
                            float *d_nospeech, int32_t *d_anc_out, int32_t *d_pos0_out, void *d_ws, size_t ws_bytes, void *stream);
+
+/* the built-in sampling draw of the selection kernels (cfg.seed / cfg.window_uid above), through the functions those kernels call.
+ * swx_test_sampler_words: for ids id0 .. id0 + n - 1 of (seed, row_uid, step) the 32-bit hash words (d_words uint32 [n]) and the f32
+ * variates added to logits / T (d_variates f32 [n]).  swx_test_sampler_buckets: the variate of every bucket k = word >> 8 in
+ * [k0, k0 + n), k0 + n <= 2^24 (one launch may cover all 2^24: 64 MB).  row_uid is taken mod 2^32; step, id0, k0 >= 0.  Asynchronous on `stream`; 0 or a negative error. */
+int swx_test_sampler_words(uint64_t seed, int64_t row_uid, int step, int id0, int n, uint32_t *d_words, float *d_variates, void *stream);
+int swx_test_sampler_buckets(int k0, int n, float *d_variates, void *stream);
 
 #ifdef __cplusplus
 }

@@ -147,6 +147,8 @@ SYMBOLS = {
     "swx_test_decode_script": (c_int, [POINTER(swx_decode_cfg), c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                        c_void_p]),
+    "swx_test_sampler_words": (c_int, [c_uint64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "swx_test_sampler_buckets": (c_int, [c_int, c_int, c_void_p, c_void_p]),
     "swx_test_lane_xor": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "swx_test_layernorm": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "swx_test_attention": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int,

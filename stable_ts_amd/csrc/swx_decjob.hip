@@ -377,7 +377,7 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
 
 // ---- swx_test_decode_script: the selection path of swx_decode on the caller's logits (no model, no forward pass)
 namespace {
-struct ScriptLayout { DecodeStateOff dec; size_t logits, total; };
+struct ScriptLayout { DecodeStateOff dec; size_t logits, win_uid, total; };
 ScriptLayout script_layout(int W, int G, int V, int n_ctx)
 {
     const size_t M = (size_t)W * G;
@@ -386,6 +386,7 @@ ScriptLayout script_layout(int W, int G, int V, int n_ctx)
     auto take = [&](size_t bytes) { size_t o = cur; cur = align_up(cur + bytes); return o; };
     swx_decode_state_layout(take, W, M, (size_t)n_ctx + 1, n_ctx, W, L.dec);
     L.logits = take(M * (size_t)V * 4);
+    L.win_uid = take((size_t)W * 4);
     L.total = cur;
     return L;
 }
@@ -430,7 +431,8 @@ int swx_test_decode_script(const swx_decode_cfg *cfg, int n_vocab, int n_ctx, co
     // The binding shared with swx_decode, on this hook's own layout of the caller's buffer.  This caller's own: the null-pointer
     // checks and the buffer's size / alignment (-8) above; the suppress count and the token ids looked at BEFORE the binding, because
     // here they come ahead of the buffer check (-8) and the initial-token check (-1); the suppress list is the caller's pointer, not
-    // a copy; no window_uid; `begin` holds the W lengths alone and is uploaded synchronously.
+    // a copy; window_uid is uploaded into the layout's own W-int slot, as swx_decode uploads it into the workspace's; `begin` holds the
+    // W lengths alone and is uploaded synchronously.
     DecodeBufs b;
     const int brc = bind_decode_job(*cfg, V, n_ctx, n_init, ws, L.dec, (float *)(ws + L.logits), b);
     if (brc < 0) return brc;
@@ -443,6 +445,13 @@ int swx_test_decode_script(const swx_decode_cfg *cfg, int n_vocab, int n_ctx, co
         if (er == hipSuccess) er = hipStreamSynchronize(s);          // the caller's array may be freed when this call returns
         if (er != hipSuccess) return -100 - (int)er;
         b.begin = d_begin;
+    }
+    if (cfg->window_uid) {
+        int32_t *d_uid = (int32_t *)(ws + L.win_uid);
+        er = hipMemcpyAsync(d_uid, cfg->window_uid, (size_t)W * 4, hipMemcpyHostToDevice, s);
+        if (er == hipSuccess) er = hipStreamSynchronize(s);          // the caller's array may be freed when this call returns
+        if (er != hipSuccess) return -100 - (int)er;
+        b.win_uid = d_uid;
     }
     er = hipMemsetAsync(b.win_done_prev, 0, (size_t)W * 4, s);
     if (er != hipSuccess) return -100 - (int)er;

@@ -31,6 +31,34 @@ struct DecodeBufs {
     const int32_t *win_uid;    // [W] stable window identities for the sampling RNG, or null (= window index)
 };
 
+// ---- the built-in sampling draw (temperature > 0, cfg.noise == NULL): one Gumbel variate per (seed, row_uid, step, token id).
+// Here, not in swx_decode.hip, so that the test hooks (swx_test_sampler_words / _buckets) run the very functions the selection
+// kernels call.  Contract (swx.h, tests/sampler_ref.py): bucket k = word >> 8, u_k = (k + 0.5) * 2^-24, variate -ln(-ln u_k).
+__device__ __forceinline__ unsigned hash32(unsigned x)
+{
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+
+__device__ __forceinline__ unsigned sampler_word(uint64_t seed, unsigned row_uid, unsigned step, unsigned idx)
+{
+    const unsigned h = hash32((unsigned)seed ^ hash32(idx + 0x9e3779b9u * (step + 1u)));
+    return hash32(h ^ hash32(row_uid * 0x85ebca6bu + (unsigned)(seed >> 32)));
+}
+
+// f32 has no 24-bit bucket centre from 0.5 up (k + 0.5f rounds to even there), and in the top bucket the rounded centre is 1.0f,
+// whose variate would be +inf: u is held at the largest f32 below 1.  Every other bucket's bits are what they always were.
+__device__ __forceinline__ float sampler_variate(unsigned word)
+{
+    const float u = fminf(((float)(word >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);   // (0,1)
+    return -logf(-logf(u));
+}
+
+__device__ __forceinline__ float gumbel(uint64_t seed, unsigned row_uid, unsigned step, unsigned idx)
+{
+    return sampler_variate(sampler_word(seed, row_uid, step, idx));
+}
+
 int swx_decode_init(const DecodeBufs &b, const int32_t *init_tokens, hipStream_t s);
 int swx_decode_after_prefill(const DecodeBufs &b, const float *lg2, float *nospeech, hipStream_t s);
 int swx_decode_select(const DecodeBufs &b, int cur, hipStream_t s);

@@ -97,19 +97,7 @@ __device__ float block_sum(float x, float *sh)
     return r;
 }
 
-__device__ __forceinline__ unsigned hash32(unsigned x)
-{
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-
-__device__ __forceinline__ float gumbel(uint64_t seed, unsigned row_uid, unsigned step, unsigned idx)
-{
-    unsigned h = hash32((unsigned)seed ^ hash32(idx + 0x9e3779b9u * (step + 1u)));
-    h = hash32(h ^ hash32(row_uid * 0x85ebca6bu + (unsigned)(seed >> 32)));
-    const float u = ((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0,1)
-    return -logf(-logf(u));
-}
+// (hash32, sampler_word, sampler_variate, gumbel: the built-in sampling draw lives in swx_decode.h, shared with its test hooks)
 
 // Number of initial tokens of window w: the job's common value, or the window's own in a ragged job (DecodeBufs::begin).  The
 // step counter is common to all windows either way -- window w holds begin + step tokens when unit `step` selects.

@@ -53,9 +53,44 @@ __global__ __launch_bounds__(256) void gelu_pair_check_kernel(unsigned long long
     if (nan_bits) atomicAdd(out + 2, (unsigned long long)nan_bits);
 }
 
+// the built-in sampling draw (swx_decode.h) as the selection kernels call it: the word and its variate of ids id0 .. id0 + n - 1
+// (swx_test_sampler_words), the variate of every bucket k0 .. k0 + n - 1 (swx_test_sampler_buckets)
+__global__ __launch_bounds__(256) void sampler_words_kernel(uint64_t seed, unsigned row_uid, unsigned step, unsigned id0, unsigned n,
+                                                            uint32_t *__restrict__ words, float *__restrict__ variates)
+{
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    words[i] = sampler_word(seed, row_uid, step, id0 + i);
+    variates[i] = gumbel(seed, row_uid, step, id0 + i);
+}
+
+__global__ __launch_bounds__(256) void sampler_buckets_kernel(unsigned k0, unsigned n, float *__restrict__ variates)
+{
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    variates[i] = sampler_variate((k0 + i) << 8);
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------------------------------------ test hooks
+int swx_test_sampler_words(uint64_t seed, int64_t row_uid, int step, int id0, int n, uint32_t *d_words, float *d_variates, void *stream)
+{
+    if (!d_words || !d_variates || n <= 0 || step < 0 || id0 < 0 || (int64_t)id0 + n > (int64_t)1 << 31) return -1;
+    hipLaunchKernelGGL(sampler_words_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, S(stream), seed, (unsigned)(uint64_t)row_uid,
+                       (unsigned)step, (unsigned)id0, (unsigned)n, d_words, d_variates);
+    SWX_CHECK_LAUNCH();
+    return 0;
+}
+
+int swx_test_sampler_buckets(int k0, int n, float *d_variates, void *stream)
+{
+    if (!d_variates || n <= 0 || k0 < 0 || (int64_t)k0 + n > (int64_t)1 << 24) return -1;
+    hipLaunchKernelGGL(sampler_buckets_kernel, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, S(stream), (unsigned)k0, (unsigned)n, d_variates);
+    SWX_CHECK_LAUNCH();
+    return 0;
+}
+
 int swx_test_gemm(int dtype, const void *d_a, int64_t lda, const void *d_w, const float *d_bias, const void *d_res,
                   void *d_c, int64_t ldc, int M, int N, int K, int epilogue, int force_kernel, void *stream)
 {

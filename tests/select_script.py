@@ -12,7 +12,12 @@ arithmetic of the kernels cannot legitimately flip one) and counts which rule br
 
 Plain helper module (no fixtures, not a conftest); tests/test_select_script_cpu.py holds the conditions on the inputs,
 tests/test_gpu_select_script.py runs the kernels on the same cases.
+
+A sampling case (temperature > 0) either supplies ``noise`` (cfg.noise, the framework's Exp(1) variates) or sets ``hashed``: the
+device then draws with its built-in hashed sampler (noise = NULL, cfg.seed, cfg.window_uid) and the reference is fed the float64
+statement of that sampler's Exp(1) variates (tests/sampler_ref.py).
 """
+import functools
 from collections import Counter
 from dataclasses import dataclass, field
 from typing import List, Optional
@@ -20,6 +25,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+import sampler_ref
 from oracle import stable as ost
 from oracle.whisper import decoding as od
 
@@ -70,6 +76,11 @@ class Case:
     ts_mask: Optional[np.ndarray] = None  # uint8 [W][1501]
     noise: Optional[np.ndarray] = None    # f32 [sample_len][W * G][V]
     ties: set = field(default_factory=set)   # (window, step) with a planted exact tie: no margin is asked there
+    hashed: bool = False                  # temperature > 0 without noise: the built-in hashed draw, keyed on seed / window_uid
+    seed: int = 0                         # cfg.seed
+    window_uid: Optional[tuple] = None    # cfg.window_uid [W]
+    planted: Optional[tuple] = None       # (step, row, id) a case is built around
+    _q: Optional[np.ndarray] = None
 
     blank: int = -1                       # >= 0: the id of " " where the stand-in's is not the tokenizer's
 
@@ -83,6 +94,25 @@ class Case:
     @property
     def begins(self):
         return [len(t) for t in self.init]
+
+    def draw_q(self, w, i):
+        """the Exp(1) variates [G][V] the G rows of window w draw token i with: cfg.noise, or the hashed sampler's statement"""
+        if self.noise is None:
+            assert self.hashed, "a sampling case gives cfg.noise or asks for the hashed draw (hashed=True): it has neither"
+            if self._q is None:
+                self._q = sampler_ref.job_q(self.seed, self.sample_len, self.W, self.G, self.V, self.window_uid)
+            return self._q[i, w * self.G:(w + 1) * self.G]
+        assert not self.hashed, "cfg.noise replaces the hashed draw: a case has one or the other"
+        return self.noise[i, w * self.G:(w + 1) * self.G]
+
+    def draw_slack(self, w, i):
+        """[G][V] or None: how far the variate of each id lies from its neighbouring buckets' (hashed draw only)"""
+        if not self.hashed:
+            return None
+        k = sampler_ref.bucket(sampler_ref.job_words(self.seed, self.sample_len, self.W, self.G, self.V, self.window_uid)[i, w * self.G:(w + 1) * self.G])
+        k = k.astype(np.int64)
+        g = sampler_ref.g_of_bucket
+        return np.maximum(g(np.minimum(k + 1, sampler_ref.N_BUCKETS - 1)) - g(k), g(k) - g(np.maximum(k - 1, 0)))
 
     def logits(self, w, i):
         """the raw logits the G rows of window w select token i from"""
@@ -139,18 +169,27 @@ class _LogSoftmaxTap:
 
 
 class _NoiseDraw:
-    """stands where decoding.py's ``Categorical`` stands when the case supplies cfg.noise: the multinomial draw the framework makes
-    from Exp(1) variates q, argmax_i(logits_i / T - log q_i), in float64"""
+    """stands where decoding.py's ``Categorical`` stands: the multinomial draw the framework makes from Exp(1) variates q (cfg.noise,
+    or the float64 statement of the hashed sampler's), argmax_i(logits_i / T - log q_i), in float64.  The margin it measures is
+    that of the winner's key LESS its slack over every other key PLUS its slack: no slack with cfg.noise (the device reads the
+    same f32 numbers); for the hashed draw, the distance to the neighbouring buckets' variates -- what the f32 variate of the
+    device may be off by (one bucket: tests/test_gpu_sampler.py), next to nothing mid-range and up to 1.1 in the outermost
+    buckets, so that no case leans on a draw from the far tails"""
     noise = None
+    slack = None
     margins = None
 
     def __init__(self, logits):
         self.key = logits.double() - torch.log(torch.from_numpy(np.ascontiguousarray(_NoiseDraw.noise)).double())
 
     def sample(self):
-        top = self.key.topk(2, dim=-1).values
-        _NoiseDraw.margins.extend((top[:, 0] - top[:, 1]).tolist())
-        return self.key.argmax(dim=-1)
+        pick = self.key.argmax(dim=-1)
+        slack = torch.zeros_like(self.key) if _NoiseDraw.slack is None else torch.from_numpy(np.ascontiguousarray(_NoiseDraw.slack))
+        rows = torch.arange(self.key.shape[0])
+        others = self.key + slack
+        others[rows, pick] = -np.inf
+        _NoiseDraw.margins.extend(((self.key[rows, pick] - slack[rows, pick]) - others.max(dim=-1).values).tolist())
+        return pick
 
 
 @dataclass
@@ -268,8 +307,7 @@ def _run_window(case, w, counts, margins):
                     if live[g] and not tied(i):
                         note("argmax", i, top[g, 0] - top[g, 1])
             else:
-                assert case.noise is not None, "a sampling case needs cfg.noise: the reference cannot follow the hashed draw"
-                _NoiseDraw.noise, _NoiseDraw.margins = case.noise[i, w * G:(w + 1) * G], []
+                _NoiseDraw.noise, _NoiseDraw.slack, _NoiseDraw.margins = case.draw_q(w, i), case.draw_slack(w, i), []
             if (~live).any() and live.any():
                 counts["row_past_eot"] += 1
             od.Categorical, keep = _NoiseDraw, od.Categorical
@@ -579,6 +617,74 @@ def case_sampling(V, seed=7):
                 noise=noise)
 
 
+HASH_HI = 0x5BD1E995       # high half of the hashed cases' cfg.seed: both halves are non-zero
+UIDS = (7, 3_000_000)      # window uids of the uid-keyed variants
+# low half of cfg.seed per (V, T, keyed): counted up from 1 on the CPU until the reference alone meets the margin condition
+# (tests/test_select_script_cpu.py); default 1
+_HASH_LO = {}
+
+
+def case_hashed_sampling(V, T, window_uid=None, seed=12):
+    """best-of 3 in two windows drawn by the BUILT-IN hashed sampler (noise = NULL on the device): every row offers eight tokens
+    within 1.0 of one another above the background, so that at T = 1 the draw spreads over all eight (and now and then over the
+    background), at T = 0.2 over the best few; two rows are offered EOT on the way and stop accumulating where they take it"""
+    tok = Tok(V)
+    W, G, S = 2, 3, 6
+    rng, prefill, script = _base(V, W, G, S - 1, seed)
+    pool = np.arange(260, tok.eot - 1) if tok.eot > 400 else np.arange(tok.timestamp_begin + 10, V - 10)
+    for w in range(W):
+        for i in range(S):
+            for g in range(1 if i == 0 else G):
+                row = _row((prefill, script), w, G, i, None if i == 0 else g)
+                row[rng.choice(pool, 8, replace=False)] = rng.uniform(11.0, 12.0, 8).astype(np.float32)
+                if (w, g, i) in ((0, 0, 1), (1, 2, 3)):
+                    row[tok.eot] = 14.0
+    keyed = window_uid is not None
+    lo = _HASH_LO.get((V, T, keyed), 1)
+    return Case(f"hashed_T{T}{'_uid' if keyed else ''}_V{V}", V, 12, W, G, S, [_init(tok, 3) + [tok.no_timestamps]] * W, prefill,
+                script, temperature=T, hashed=True, seed=(HASH_HI << 32) | lo, window_uid=window_uid)
+
+
+LEAD = 18.0                # the clear lead of the top-bucket cases: a background token (< 0) would need a variate 18 above the lead's
+
+
+@functools.lru_cache(maxsize=None)
+def _top_bucket_tuple(V):
+    """(seed, step, row, id): the first seed HASH_HI << 32 | 1, 2, ... under which a (step <= 4, row < 6, id < V) of a 2 x 3 job
+    draws the TOP bucket of the hashed sampler -- and the id is no token the case needs for itself"""
+    tok = Tok(V)
+    lo = 1
+    while True:
+        hit = sampler_ref.find_top_bucket(5, 2, 3, V, 4, range(lo, 1 << 20), hi=HASH_HI)
+        assert hit is not None
+        if hit[3] not in (tok.eot, 7, 300, 301):
+            return hit
+        lo = (hit[0] & 0xFFFFFFFF) + 1
+
+
+def case_top_bucket(V, suppressed, seed=13):
+    """the hashed draw's top bucket (u nearest 1, the largest variate: 17.33 by the contract) falls on a token that must not win:
+    id X of one row at one step, at T = 1, while token 300 leads that row by far.  `suppressed`: X is on the suppress list (masked,
+    no variate may lift it); otherwise X is allowed but 30 below the lead, more than any finite variate spans (-2.86 .. 17.33).
+    A sampler whose top bucket is not finite selects X"""
+    tok = Tok(V)
+    W, G, S = 2, 3, 5
+    hseed, step, row, x = _top_bucket_tuple(V)
+    rng, prefill, script = _base(V, W, G, S - 1, seed)
+    for w in range(W):
+        for i in range(S):
+            r = _row((prefill, script), w, G, i)
+            r[..., 300 + (i & 1)] = LEAD
+            if not suppressed and w == row // G:
+                if i == 0 and step == 0:
+                    r[x] = LEAD - 30.0            # (step 0: the window's rows share the prefill row)
+                elif i == step and i > 0:
+                    r[row % G, x] = LEAD - 30.0
+    return Case(f"top_bucket_{'suppressed' if suppressed else 'far_below'}_V{V}", V, 12, W, G, S,
+                [_init(tok, 3) + [tok.no_timestamps]] * W, prefill, script, temperature=1.0, hashed=True, seed=hseed,
+                suppress=(7, x) if suppressed else (), planted=(step, row, x))
+
+
 # seeds chosen on the CPU until the reference alone meets the margin condition (tests/test_select_script_cpu.py); default 8
 _BEAM_SEED = {("_b", 5, 1.0, 51865): 9, ("_c", 5, 1.0, 51865): 10, ("_c", 5, 1.0, 1601): 17, ("_b", 5, 2.0, 1601): 55}
 
@@ -652,6 +758,11 @@ def all_cases():
             yield lambda V=V, kind=kind: case_nonfinite(V, kind)
         yield lambda V=V: case_greedy_completion(V)
         yield lambda V=V: case_sampling(V)
+        for T in (0.2, 1.0):
+            yield lambda V=V, T=T: case_hashed_sampling(V, T)
+        yield lambda V=V: case_hashed_sampling(V, 1.0, UIDS)
+        yield lambda V=V: case_top_bucket(V, True)
+        yield lambda V=V: case_top_bucket(V, False)
         # (a) a window completes early and is frozen, (b) fewer than G finish, (c) more EOT arrive than there is room for
         yield lambda V=V: case_beam(V, 2, 1.0, {(0, 2): (0, 1)}, W=2, sample_len=6, tag="_a")
         yield lambda V=V: case_beam(V, 5, 1.0, {(0, 1): (0,)}, tag="_b")

@@ -6,6 +6,10 @@ memory-walking kernel (debug flag 8192); both must equal the reference, not mere
 Exact: tokens, lens (-1 slots included), steps executed, ancestor table, pos0.  sum_logprobs: atol 1e-4 (at most 24 steps of a few
 f32 ulp at magnitude <= 30; scripted finite logits lie in [-20, 20]); no_speech_prob: 1e-4 + 1e-2 * ref.  The decision margins of
 every case are >= 1e-3 in float64 (tests/test_select_script_cpu.py), so no f32 rounding can move a decision.
+
+The hashed_* and top_bucket_* cases run the kernels' BUILT-IN sampling draw (noise = NULL) against the float64 statement of it in
+tests/sampler_ref.py; there the margin also covers the f32 error of the variate itself, at most 4.9e-4 outside the outermost
+2^-12 of the buckets (tests/test_gpu_sampler.py).
 """
 import ctypes
 
@@ -37,12 +41,15 @@ def run_gpu(case, mem_kernel):
         init[w, :len(t)] = t
     hb = (ctypes.c_int32 * W)(*begins)
     noise = None if case.noise is None else torch.from_numpy(case.noise).to(dev)
+    # (a hashed case: noise stays NULL and the kernels draw from cfg.seed / cfg.window_uid)
+    uid = None if case.window_uid is None else (ctypes.c_int32 * W)(*case.window_uid)
     cfg = _lib.swx_decode_cfg(
         n_windows=W, n_group=G, beam=case.beam, temperature=case.temperature, patience=case.patience,
         sample_len=case.sample_len, sample_begin=n_init, sot_index=0, suppress_blank=case.suppress_blank,
         apply_timestamp_rules=case.rules, max_initial_timestamp_index=case.max_initial, eot=tok.eot, sot=tok.sot,
         no_timestamps=tok.no_timestamps, timestamp_begin=tok.timestamp_begin, no_speech=tok.no_speech, blank_token=tok.blank,
-        n_suppress=len(case.suppress), min_tokens=case.min_tokens, seed=0, window_uid=None,
+        n_suppress=len(case.suppress), min_tokens=case.min_tokens, seed=case.seed,
+        window_uid=None if uid is None else ctypes.cast(uid, ctypes.POINTER(ctypes.c_int32)),
         noise=noise.data_ptr() if noise is not None else None,
         sample_begins=ctypes.cast(hb, ctypes.POINTER(ctypes.c_int32)) if min(begins) != n_init else None, sot_indices=None)
     d_init = torch.from_numpy(init).to(dev)

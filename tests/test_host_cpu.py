@@ -365,19 +365,20 @@ _WORKSPACE_BYTES = {
     ("large-v3", 1, 20, 100): 25817587456,
     ("large-v3", 1, 3, 48): 6304072448,
 }
+# (each 256 bytes more than the hand-written list had: the W-int slot of the window uids, behind the logits)
 _SCRIPT_WS_BYTES = {
-    (1, 1, 51865, 448): 276224,
-    (1, 1, 51865, 16): 214272,
-    (1, 1, 97, 448): 69120,
-    (1, 1, 97, 16): 7168,
-    (3, 5, 51865, 448): 3397888,
-    (3, 5, 51865, 16): 3128064,
-    (3, 5, 97, 448): 291840,
-    (3, 5, 97, 16): 22016,
-    (2, 16, 51865, 448): 6991104,
-    (2, 16, 51865, 16): 6659328,
-    (2, 16, 97, 448): 364800,
-    (2, 16, 97, 16): 33024,
+    (1, 1, 51865, 448): 276480,
+    (1, 1, 51865, 16): 214528,
+    (1, 1, 97, 448): 69376,
+    (1, 1, 97, 16): 7424,
+    (3, 5, 51865, 448): 3398144,
+    (3, 5, 51865, 16): 3128320,
+    (3, 5, 97, 448): 292096,
+    (3, 5, 97, 16): 22272,
+    (2, 16, 51865, 448): 6991360,
+    (2, 16, 51865, 16): 6659584,
+    (2, 16, 97, 448): 365056,
+    (2, 16, 97, 16): 33280,
 }
 
 

@@ -2,7 +2,8 @@
 
 * every decision margin the reference measures in float64 is at least 1e-3 (100 times the f32 log-softmax error at the
   magnitudes used), so the kernels' f32 arithmetic cannot legitimately decide otherwise; planted exact ties are excepted, they
-  are bit-equal on both sides;
+  are bit-equal on both sides; the margin of a draw by the built-in hashed sampler is measured after every key has given up its
+  distance to the neighbouring buckets' variates (the device's f32 variate may sit one bucket off in the far tails);
 * finite scripted logits lie in [-20, 20] (the sum_logprobs tolerance of the GPU test is worked out for that);
 * over the whole case list every rule branch the GPU test is meant to reach is reached at least once;
 * the helper follows ``_main_loop``: fed the logits a small real decoder produced, it reproduces ``oracle.stable.decode_stable``.
@@ -69,7 +70,8 @@ def test_layouts_and_kinds_are_all_present(survey):
     for V in ss.RULE_LAYOUTS:
         mine = [n for n in names if n.endswith(f"_V{V}")]
         for kind in ("rules_mi-1", "rules_mi0", "rules_mi50", "filters", "ts_mask_pick", "ts_mask_all", "nonfinite_nan",
-                     "nonfinite_pinf", "nonfinite_ninf", "nonfinite_all", "greedy_eot", "sampling", "beam_a_G2_p1.0",
+                     "nonfinite_pinf", "nonfinite_ninf", "nonfinite_all", "greedy_eot", "sampling", "hashed_T0.2_V", "hashed_T1.0_V",
+                     "hashed_T1.0_uid", "top_bucket_suppressed", "top_bucket_far_below", "beam_a_G2_p1.0",
                      "beam_b_G5_p1.0", "beam_c_G5_p1.0", "beam_c_G2_p2.0", "beam_b_G2_p2.0", "beam_b_G5_p2.0", "ragged",
                      "poll_exit", "ctx_exact", "beam_ctx"):
             assert any(n.startswith(kind) for n in mine), (V, kind)
@@ -103,6 +105,16 @@ def test_expected_outcomes_of_the_planted_cases(survey):
         assert r.steps == 9 and r.lens[0, 0] == 9 and r.pos0.tolist() == [11]
         r = by[f"beam_b_G2_p2.0_V{V}"]
         assert r.lens[0].tolist().count(-1) == 2
+        # the hashed sampler's top bucket on a token that must not win: the lead is selected at that very (step, row)
+        for kind in ("suppressed", "far_below"):
+            c = ss.case_top_bucket(V, kind == "suppressed")
+            step, row, x = c.planted
+            assert step <= 4 and ss.sampler_ref.bucket(ss.sampler_ref.words(c.seed, row, step, x)) == (1 << 24) - 1
+            r = by[f"top_bucket_{kind}_V{V}"]
+            assert r.tokens[row // c.G, row % c.G, 4 + step] == 300 + (step & 1) != x
+            assert (x in c.suppress) == (kind == "suppressed") and c.noise is None and c.seed >> 32 and c.seed & 0xFFFFFFFF
+            if kind == "far_below":
+                assert c.logits(row // c.G, step)[row % c.G, x] == ss.LEAD - 30.0 and c.logits(row // c.G, step)[row % c.G].max() == ss.LEAD
         # NaN in the text range: the reference keeps the text tokens (its log-softmax is NaN everywhere) and picks the best one
         r = by[f"nonfinite_nan_V{V}"]
         assert r.tokens[0, 0, 6] == 32 and r.tokens[1, 0, 6] == 32 and r.tokens[2, 0, 6] == 32
