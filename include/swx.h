@@ -530,6 +530,11 @@ int swx_test_dec_plan(int M, int N, int K, int epilogue, int flags);
  * with W = 1; cnt, gathered and rstat are empty (their offsets are those of the region that follows). */
 int swx_test_heads_layout(const swx_model *m, int W, int max_n, int count, int64_t *out);
 
+/* the bookkeeping behind every raise of a kernel's dynamic-LDS limit (csrc/swx_common.h::SwxLdsGrants: one table per kernel, one entry
+ * per device 0..63; host-only, no GPU): on a fresh table, record (dev[i], ok[i] != 0 = granted, 0 = refused) for i = 0 .. n - 1 in
+ * order, then state_out[d] for d = 0..63 = 0 unknown, 1 granted, -1 refused.  -5 and nothing written when a dev[i] lies outside 0..63. */
+int swx_test_lds_grants(const int *dev, const int *ok, int n, int *state_out);
+
 /* the VALU lane-exchange helpers of csrc/swx_common.h (v_permlane16/32_swap, DPP) against __shfl_xor, on n_waves waves of 64
  * u32 values: d_out[((w * 13 + k) * 64) + lane], k = 0..5 lane_xor<32, 16, 8, 4, 2, 1>, k = 6..11 the __shfl_xor of the same
  * offsets, k = 12 a bit mask of the derived forms that agreed with their shuffle form (1 wave_sum_d, 2 / 4 lane_xor16_max / 32_max,

@@ -161,6 +161,7 @@ SYMBOLS = {
                                           c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_int, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "swx_test_xattn_plan": (c_int, [c_int] * 9),
+    "swx_test_lds_grants": (c_int, [POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int)]),
 }
 
 _lib = None

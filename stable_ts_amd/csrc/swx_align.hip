@@ -178,14 +178,8 @@ int swx_align_weights_launch(const float *d_qk, float *d_p, float *d_mean, float
 #define SWX_FUSED(WD) do { \
         constexpr int NC_ = AL_FT + 2 * (WD / 2); \
         const size_t lds = (((size_t)N * (NC_ + 1) * 4 + 15) & ~(size_t)15) + (size_t)4 * NC_ * 2 * 8 + (size_t)2 * NC_ * 4; \
-        static bool attr_done = false; \
-        if (!attr_done) { \
-            hipError_t e_ = hipFuncSetAttribute((const void *)swx_align_fused_kernel<WD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024); \
-            if (e_ != hipSuccess) return -100 - (int)e_; \
-            attr_done = true; \
-        } \
-        hipLaunchKernelGGL(swx_align_fused_kernel<WD>, g, dim3(256), lds, s, d_qk, rstat, d_neg_matrix, H, N, ld_f, out_ld_n, out_ld_f, \
-                           d_n_rows, d_n_frames, qk_scale); } while (0)
+        if (int rc_ = swx_launch_lds<swx_align_fused_kernel<WD>>(g, dim3(256), lds, SWX_LDS_MAX, s, d_qk, rstat, d_neg_matrix, H, N, ld_f, out_ld_n, \
+                                                                 out_ld_f, d_n_rows, d_n_frames, qk_scale)) return rc_; } while (0)
     switch (medfilt_width) {
         case 1: SWX_FUSED(1); break;
         case 3: SWX_FUSED(3); break;

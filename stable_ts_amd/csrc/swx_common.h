@@ -1,9 +1,10 @@
-// swx_common.h -- shared device helpers for the gfx950 kernels of libswx.so
+// swx_common.h -- shared device helpers for the gfx950 kernels of libswx.so, and the one launcher of kernels with large dynamic LDS
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 #include <math.h>
+#include <atomic>
 
 #define SWX_WAVE 64
 
@@ -16,6 +17,52 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define SWX_CHECK_LAUNCH() do { hipError_t _e = hipGetLastError(); if (_e != hipSuccess) return -100 - (int)_e; } while (0)
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// ---- dynamic LDS above the 64 KB a launch gets unasked: one grant per (kernel, device) ---------------------------------------
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the DEVICE's copy of a kernel's code object: a process that drives several
+// GPUs has to raise it on each, and one kernel's grant says nothing about another's.  SwxLdsGrants is the bookkeeping of ONE kernel
+// (no HIP calls: swx_test_lds_grants drives it on the host): per device 0..63 unknown (0), granted (1) or refused (-1).  Relaxed
+// atomics, no lock: two threads that both find "unknown" both set the attribute, which is harmless.  A device index outside 0..63
+// is never remembered (state 0: the attribute is set again on every launch).
+struct SwxLdsGrants {
+    std::atomic<uint64_t> granted{0}, refused{0};
+    static bool tracked(int dev) { return dev >= 0 && dev < 64; }
+    int state(int dev) const
+    {
+        if (!tracked(dev)) return 0;
+        const uint64_t bit = uint64_t(1) << dev;
+        return (granted.load(std::memory_order_relaxed) & bit) ? 1 : (refused.load(std::memory_order_relaxed) & bit) ? -1 : 0;
+    }
+    void record(int dev, bool ok)
+    {
+        if (tracked(dev)) (ok ? granted : refused).fetch_or(uint64_t(1) << dev, std::memory_order_relaxed);
+    }
+};
+// raises Kernel's dynamic-LDS limit to max_bytes on the current device, the first time it is asked there.  A refusal is remembered
+// too (the sticky error cleared): the device is asked once, and every later call reports hipErrorInvalidValue.  The ONE place in
+// csrc/ that sets the attribute (tests/test_lds_grants_cpu.py).
+template <auto Kernel> hipError_t swx_lds_grant(int max_bytes)
+{
+    static SwxLdsGrants grants;               // of this instantiation = of this kernel (constant-initialised)
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const int st = grants.state(dev);
+    if (st != 0) return st > 0 ? hipSuccess : hipErrorInvalidValue;
+    e = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_bytes);
+    if (e != hipSuccess) (void)hipGetLastError();
+    grants.record(dev, e == hipSuccess);
+    return e;
+}
+// grant, then launch.  0, or -100 - the grant's error; launch errors are the caller's SWX_CHECK_LAUNCH as for every other launch
+template <auto Kernel, class... A> int swx_launch_lds(dim3 grid, dim3 block, size_t lds, int max_bytes, hipStream_t s, A... args)
+{
+    const hipError_t e = swx_lds_grant<Kernel>(max_bytes);
+    if (e != hipSuccess) return -100 - (int)e;
+    hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+    return 0;
+}
+constexpr int SWX_LDS_MAX = 160 * 1024 - 1024;      // what the kernels that size their LDS at run time ask for: a CU's 160 KB less 1 KB
 
 template <typename T> __device__ __forceinline__ float to_f32(T v);
 template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }

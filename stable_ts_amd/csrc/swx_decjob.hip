@@ -212,7 +212,7 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
     // row the same way whatever the launch (tests/test_gpu_batch_invariance.py).  One more choice does follow the PADDED length:
     // swx_self_attention takes self_attn_cached below 8 new tokens, self_attn_cached_mq_f16<4> for 8-31, <8> from 32 on -- a window
     // of 5 tokens next to one of 12 runs another self-attention kernel than alone.  Those three are bit-identical by construction
-    // (one arithmetic order, swx_attn.hip) and that is RELIED upon here; tests/test_gpu_ragged_decode.py has neighbours on both
+    // (one arithmetic order, swx_selfattn.hip) and that is RELIED upon here; tests/test_gpu_ragged_decode.py has neighbours on both
     // sides of 8 and of 32.  Rows past a window's own length are computed
     // and never read: causal attention keeps them out of the real rows, and their K/V slots are overwritten by the window's
     // first sampled tokens before a step attends to them.
@@ -311,7 +311,7 @@ int swx_decode(swx_model *m, const swx_decode_cfg *cfg, const int32_t *d_init_to
         // a property of the job, not of the step: safe to bake into the graph.  Ragged job: the LONGEST window's bound, so a short
         // window that alone takes self_attn_step_f16<false> (bound <= 128) takes the <true> / deep variant here: the step kernel of
         // a row then depends on the job.  The variants differ only in code for positions >= 128 that such a row never reaches and
-        // are bit-identical below (swx_attn.hip); that identity is RELIED upon (tests/test_gpu_ragged_decode.py: 1 next to 228)
+        // are bit-identical below (swx_selfattn.hip); that identity is RELIED upon (tests/test_gpu_ragged_decode.py: 1 next to 228)
         g.pos_bound = n_init + cfg->sample_len;
         const int fr = swx_decoder_forward(m, g, st);
         if (fr < 0) return fr;

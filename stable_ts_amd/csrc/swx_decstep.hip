@@ -688,22 +688,9 @@ int swx_gemm_dec(DecGemmArgs g, hipStream_t s)
         const int grid = cdiv(units, 8) * g.n_rg * 8;
         const size_t lds = (size_t)3 * 16 * g.kslice * 2 + 3 * 16 * sizeof(float2);
         SwxProfScope prof(PC_GEMM_SKINNY, 2.0 * ((double)g.N * g.K + (double)g.M * g.K) + (double)g.M * g.N * 2, s);
-#define SWX_TALL(NK_, EP_) do { \
-        static bool attr_done = false; \
-        if (!attr_done) { \
-            hipError_t e_ = hipFuncSetAttribute((const void *)gemm_dectall_f16<NK_, EP_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024); \
-            if (e_ != hipSuccess) return -100 - (int)e_; \
-            attr_done = true; \
-        } \
-        hipLaunchKernelGGL((gemm_dectall_f16<NK_, EP_>), dim3(grid), dim3(256), lds, s, g); } while (0)
-#define SWX_TALL8(NK_, EP_) do { \
-        static bool attr_done8 = false; \
-        if (!attr_done8) { \
-            hipError_t e_ = hipFuncSetAttribute((const void *)gemm_dectall_f16<NK_, EP_, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024); \
-            if (e_ != hipSuccess) return -100 - (int)e_; \
-            attr_done8 = true; \
-        } \
-        hipLaunchKernelGGL((gemm_dectall_f16<NK_, EP_, 8>), dim3(grid), dim3(512), lds, s, g); } while (0)
+        // (dynamic LDS past 64 KB: one grant per kernel and device, swx_common.h)
+#define SWX_TALL(NK_, EP_) do { if (int rc_ = swx_launch_lds<gemm_dectall_f16<NK_, EP_>>(dim3(grid), dim3(256), lds, SWX_LDS_MAX, s, g)) return rc_; } while (0)
+#define SWX_TALL8(NK_, EP_) do { if (int rc_ = swx_launch_lds<gemm_dectall_f16<NK_, EP_, 8>>(dim3(grid), dim3(512), lds, SWX_LDS_MAX, s, g)) return rc_; } while (0)
 #define SWX_TALL_NK(EP_) do { if (w8) { switch (nks) { \
         case 16: SWX_TALL8(16, EP_); break; case 24: SWX_TALL8(24, EP_); break; case 32: SWX_TALL8(32, EP_); break; case 40: SWX_TALL8(40, EP_); break; \
         default: return -4; } } else { switch (nks) { \
@@ -730,22 +717,8 @@ int swx_gemm_dec(DecGemmArgs g, hipStream_t s)
     {   // (profiler scopes must not nest: each one closes the most recent record)
     SwxProfScope prof(PC_GEMM_SKINNY, 2.0 * ((double)g.N * g.K + (double)g.M * g.K) + (double)g.M * g.N * 2, s);
     // the epilogues the decoder step uses (compile-time): QKV, out-projections, cross-q, MLP-in, MLP-out (split / un-split)
-#define SWX_DEC(MT_, NK_, EP_) do { \
-        static bool attr_done = false; \
-        if (!attr_done) { \
-            hipError_t e_ = hipFuncSetAttribute((const void *)gemm_dec_f16<MT_, NK_, EP_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024); \
-            if (e_ != hipSuccess) return -100 - (int)e_; \
-            attr_done = true; \
-        } \
-        hipLaunchKernelGGL((gemm_dec_f16<MT_, NK_, EP_>), dim3(grid), dim3(256), lds, s, g); } while (0)
-#define SWX_DEC_W1(NK_, EP_) do { \
-        static bool attr_done1 = false; \
-        if (!attr_done1) { \
-            hipError_t e_ = hipFuncSetAttribute((const void *)gemm_dec_f16<1, NK_, EP_, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024); \
-            if (e_ != hipSuccess) return -100 - (int)e_; \
-            attr_done1 = true; \
-        } \
-        hipLaunchKernelGGL((gemm_dec_f16<1, NK_, EP_, 1>), dim3(grid1), dim3(64), lds, s, g); } while (0)
+#define SWX_DEC(MT_, NK_, EP_) do { if (int rc_ = swx_launch_lds<gemm_dec_f16<MT_, NK_, EP_>>(dim3(grid), dim3(256), lds, SWX_LDS_MAX, s, g)) return rc_; } while (0)
+#define SWX_DEC_W1(NK_, EP_) do { if (int rc_ = swx_launch_lds<gemm_dec_f16<1, NK_, EP_, 1>>(dim3(grid1), dim3(64), lds, SWX_LDS_MAX, s, g)) return rc_; } while (0)
 #define SWX_DEC_MT4(NK_, EP_) do { if (mt == 1) SWX_DEC(1, NK_, EP_); else if (mt == 2) SWX_DEC(2, NK_, EP_); else SWX_DEC(3, NK_, EP_); } while (0)
 #define SWX_DEC_MT(NK_, EP_) do { if (w1) SWX_DEC_W1(NK_, EP_); else SWX_DEC_MT4(NK_, EP_); } while (0)
 #define SWX_DEC_NK_(MTM_, EP_) do { switch (nks) { \

@@ -237,15 +237,9 @@ extern "C" int swx_dtw(const float *d_x, int W, int ld_n, int ld_m, const int32_
         const size_t base = 3 * D4_BR * 4 + 2 * (size_t)(ld_n + ld_m) * 4;
 #define SWX_DTW4(RR, TL) do { \
             const size_t lds = base + ((TL) ? (size_t)256 * PITCH * RR * 4 : 0); \
-            static bool attr_done4 = false; \
-            if (!attr_done4) { \
-                hipError_t e_ = hipFuncSetAttribute((const void *)swx_dtw4_kernel<RR, TL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024); \
-                if (e_ != hipSuccess) return -100 - (int)e_; \
-                attr_done4 = true; \
-            } \
-            hipLaunchKernelGGL((swx_dtw4_kernel<RR, TL>), dim3(W), dim3(256), lds, s, d_x, ld_n, ld_m, d_N, d_M, d_text_idx, d_time_idx, \
-                               d_len, (unsigned char *)d_trace_ws, per, PITCH); } while (0)
-        const bool fits = base + (size_t)256 * PITCH * 4 <= 160 * 1024 - 1024 - 64;
+            if (int rc_ = swx_launch_lds<swx_dtw4_kernel<RR, TL>>(dim3(W), dim3(256), lds, SWX_LDS_MAX, s, d_x, ld_n, ld_m, d_N, d_M, d_text_idx, \
+                                                                  d_time_idx, d_len, (unsigned char *)d_trace_ws, per, PITCH)) return rc_; } while (0)
+        const bool fits = base + (size_t)256 * PITCH * 4 <= SWX_LDS_MAX - 64;
         if (ld_n <= 256) { if (fits) SWX_DTW4(1, true); else SWX_DTW4(1, false); }
         else SWX_DTW4(2, false);
 #undef SWX_DTW4

@@ -53,7 +53,7 @@ constexpr int CLD = BN + 4;                 // f32 staging row of the epilogue
 // 8 columns for every row group of a thread) and the residual rows of a half are requested BEFORE the accumulators are
 // staged: loaded per row group after the previous group's store (a store through a f16 pointer may alias the f32 bias, so
 // hipcc keeps the order) they were eight dependent L2 round trips per tile -- 43 % of a K = 1280 launch (see below).
-// EPI_KV with GemmArgs::P (round 6): the decode-step cross-attention's fragment-ordered copy (swx_attn.hip::xkv_pack_kernel's index maps)
+// EPI_KV with GemmArgs::P (round 6): the decode-step cross-attention's fragment-ordered copy (swx_xattn.hip::xkv_pack_kernel's index maps)
 // written from the projection's epilogue.  K: the 16-byte piece (key, head, dims 8 c .. 8 c + 7) is lane (g = c & 3, qn) of fragment 2 t + (c >> 2)
 // of the key's 32-key block, key % 32 = (qn >> 2) * 8 + 4 t + (qn & 3).  V^T: the 8-byte piece (4 keys from key0 = a multiple of 4, head, dim) is
 // half (key0 % 8) / 4 of lane (g = (key0 % 32) / 8, qn = dim % 16) of fragment dim / 16.  Keys [vt_s, p_nkpad) of a head are zeros.

@@ -243,14 +243,19 @@ struct AttnArgs {
     // the key-split kernel below 17 queries, a short window's numbers would depend on the windows it shares the pass with
     int f32_no_split;
 };
+#define SWX_VT_KP 1536               // padded key count of the transposed cross-attention V (64-key tiles never run off a row)
+// dense (non-causal) attention over nk keys: encoder self-attention and cross-attention
+int swx_attention(int dtype, const AttnArgs &a, int force_kernel, hipStream_t s);
+// V [B][n][ldv] -> per-head transposed V^T [B][H][64][kp] (keys contiguous, zero padded): feeds the MFMA flash kernel's vector path
+int swx_transpose_v(const void *v, int64_t ldv, int64_t v_bs, int n, void *vt, int kp, int64_t vt_bs, int B, int H, hipStream_t s);
+int swx_pad_zero(void *base, int64_t row_bytes, int64_t batch_bytes, int off_bytes, int pad_bytes, int rows, int nb, hipStream_t s);
+
+// ---- swx_xattn.hip: the decode-step cross-attention behind swx_attention
 // fragment-ordered copy of one layer's cross K / V^T for the decode-step cross-attention: per (window, head)
 // [K: blocks of 32 keys x 4 fragments x 64 lanes x 8 halfs | V^T: the same], zero padded past nk
 __host__ __device__ inline int64_t swx_xkv_packed_elems_per_head(int nk) { return (int64_t)((nk + 31) / 32) * 4 * 512 * 2; }
 int swx_xkv_pack(const void *k, const void *vt, void *packed, int B, int H, int nk, int ldk, int vt_kp, int64_t batch_stride,
                  hipStream_t s);
-#define SWX_VT_KP 1536               // padded key count of the transposed cross-attention V (64-key tiles never run off a row)
-// dense (non-causal) attention over nk keys: encoder self-attention and cross-attention
-int swx_attention(int dtype, const AttnArgs &a, int force_kernel, hipStream_t s);
 // whether swx_attention runs a launch on the decode cross-attention kernel, and on which form of it (pure: the function the launcher
 // itself executes; swx_test_xattn_plan).  Reads the scalar fields of `a` and whether a.kv_packed / a.fq_w are set, no memory.
 // `flags`: swx_debug_flags.  family < 0: the error swx_attention returns.
@@ -260,9 +265,11 @@ enum SwxXattnFamily { SWX_XA_NOT_DECODE = 0,     // flash / f32 / row-wise kerne
                       SWX_XA_PACKED_FQ = 3 };    // attn_decode_cross_xq2_f16<FQ> (depth 2) / attn_decode_cross_xq_f16<FQ> (depth 1)
 struct SwxXattnPlan { int family, qg, depth; };  // qg: groups of 16 query rows per workgroup; depth: key blocks of a wave in flight
 SwxXattnPlan swx_xattn_plan(int dtype, const AttnArgs &a, int force_kernel, int flags);
-// V [B][n][ldv] -> per-head transposed V^T [B][H][64][kp] (keys contiguous, zero padded): feeds the MFMA flash kernel's vector path
-int swx_transpose_v(const void *v, int64_t ldv, int64_t v_bs, int n, void *vt, int kp, int64_t vt_bs, int B, int H, hipStream_t s);
-int swx_pad_zero(void *base, int64_t row_bytes, int64_t batch_bytes, int off_bytes, int pad_bytes, int rows, int nb, hipStream_t s);
+// the launch of a decode family (p.family > 0) of that plan.  Called by swx_attention alone, after its own checks of the shape and
+// of the plan's error (their order decides the code of a doubly invalid input, so they stay there)
+int swx_xattn_launch(const SwxXattnPlan &p, const AttnArgs &a, hipStream_t s);
+
+// ---- swx_selfattn.hip
 // decoder self-attention over the per-row KV cache with ancestor indirection
 struct SelfAttnArgs {
     const void *qkv; int64_t ldqkv;  // [R*n_new][3d]: q | k | v of the new tokens

@@ -133,7 +133,7 @@ inline int64_t xkv_plain_elems(const swx_dims &D)      // K [1500][d] | V^T [d][
 {
     return (int64_t)D.n_audio_ctx * D.n_text_state + (int64_t)D.n_text_state * SWX_VT_KP;
 }
-inline int64_t xkv_packed_elems(const swx_dims &D)     // f16 only: K and V^T again, in MFMA fragment order per head (swx_attn.hip)
+inline int64_t xkv_packed_elems(const swx_dims &D)     // f16 only: K and V^T again, in MFMA fragment order per head (swx_xattn.hip)
 {
     return (int64_t)D.n_text_head * swx_xkv_packed_elems_per_head(D.n_audio_ctx);
 }

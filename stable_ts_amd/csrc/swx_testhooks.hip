@@ -383,6 +383,17 @@ int swx_test_xattn_plan(int B, int H, int nq, int nk, int vt_kp, int has_packed,
     return p.family < 0 ? p.family : p.family + 16 * p.qg + 256 * p.depth;
 }
 
+int swx_test_lds_grants(const int *dev, const int *ok, int n, int *state_out)
+{
+    if (n < 0 || (n > 0 && (!dev || !ok)) || !state_out) return -1;
+    for (int i = 0; i < n; ++i)
+        if (!SwxLdsGrants::tracked(dev[i])) return -5;
+    SwxLdsGrants t;
+    for (int i = 0; i < n; ++i) t.record(dev[i], ok[i] != 0);
+    for (int d = 0; d < 64; ++d) state_out[d] = t.state(d);
+    return 0;
+}
+
 int swx_test_lane_xor(const uint32_t *d_in, uint32_t *d_out, int n_waves, void *stream)
 {
     if (!d_in || !d_out || n_waves <= 0) return -1;

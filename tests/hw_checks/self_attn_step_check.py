@@ -1,4 +1,4 @@
-"""Hardware check of the decode-step self-attention (csrc/swx_attn.hip::self_attn_step_f16<LONG>): for positions below 128 the
+"""Hardware check of the decode-step self-attention (csrc/swx_selfattn.hip::self_attn_step_f16<LONG>): for positions below 128 the
 short and the long variant, and for every position up to the end of the context the long variant, must agree BIT FOR BIT with the
 general cached-attention kernel (self_attn_cached) on the same cache, with and without an ancestor table (beam search), with
 ragged positions per row.  Round 4 batches the loads of the positions >= 128 (a decode that started from a long prompt); the

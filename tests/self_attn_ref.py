@@ -1,4 +1,4 @@
-"""Float64 statement of the decoder's cached self-attention (csrc/swx_attn.hip: self_attn_cached, kv_append_kernel,
+"""Float64 statement of the decoder's cached self-attention (csrc/swx_selfattn.hip: self_attn_cached, kv_append_kernel,
 self_attn_cached_mq_f16, self_attn_step_f16, self_attn_step_long_f16) and the inputs its tests run on.  No GPU, no library.
 
 Contract.  Grid row ``ri`` is logical row ``r = ri * row_mul``; token ``i`` of it sits at position ``pos = pos0[r] + i``.  For
@@ -25,7 +25,7 @@ N_CTX = 448
 STEP_POSITIONS = (0, 1, 7, 8, 63, 64, 127, 128, 191, 192, 255, 256, 319, 320, 383, 384, 446, 447)
 STEP_POSITIONS_SHORT = tuple(p for p in STEP_POSITIONS if p <= 127)
 RAGGED_POS0 = (0, 3, 60, 120, 440)
-MULTI_N_NEW = (1, 7, 8, 9, 31, 32, 33, 448)
+MULTI_N_NEW = (1, 7, 8, 9, 31, 32, 33, 200, 448)     # 200: the first staged length (a multiple of 8) at which MQ8 asks for more than 64 KB of LDS
 MUTATIONS = ("drop_newest", "wrong_ancestor", "head_off_by_one", "scale_0.124", "swap_v")
 
 # kernel ids of swx_test_self_attn_plan (csrc/swx_kernels.h::SwxSelfAttnKernel)

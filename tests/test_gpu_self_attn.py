@@ -1,4 +1,4 @@
-"""The cached self-attention family of the decoder (csrc/swx_attn.hip) against the float64 reference of tests/self_attn_ref.py.
+"""The cached self-attention family of the decoder (csrc/swx_selfattn.hip) against the float64 reference of tests/self_attn_ref.py.
 
 Until this file the family was tested as "bit-identical to self_attn_cached<f16>", and self_attn_cached only end to end.  Here every
 kernel -- the general kernel in f16 and f32 with its append, the multi-token kernels, the single-token step kernels with one and

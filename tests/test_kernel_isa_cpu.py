@@ -323,7 +323,11 @@ def test_reductions_exchange_lanes_on_the_valu_except_in_the_streaming_attention
     for src in ("swx_decstep.hip", "swx_decode.hip", "swx_norm.hip", "swx_align.hip"):
         bad = {k: v for k, v in _bpermutes_per_kernel(src).items() if v}
         assert not bad, (src, bad)
-    attn = _bpermutes_per_kernel("swx_attn.hip")
+    attn = {}
+    for src in ("swx_attn.hip", "swx_xattn.hip", "swx_selfattn.hip"):      # the three attention sources: one kernel lives in one of them
+        per = _bpermutes_per_kernel(src)
+        assert not set(per) & set(attn), (src, set(per) & set(attn))
+        attn.update(per)
     flash2 = {k: v for k, v in attn.items() if "attn_flash2_f16" in k}
     assert flash2 and not any(flash2.values()), flash2
     split = {k: v for k, v in attn.items() if "attn_flash_f32" in k and k.endswith("ELb1EEEv8AttnArgs")}
