@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libswx.so")
-SOURCES = ["swx_runtime.hip", "swx_decoder.hip", "swx_decjob.hip", "swx_score.hip", "swx_testhooks.hip", "swx_gemm.hip", "swx_norm.hip", "swx_attn.hip", "swx_xattn.hip", "swx_selfattn.hip", "swx_decode.hip", "swx_align.hip",
+SOURCES = ["swx_runtime.hip", "swx_decoder.hip", "swx_decjob.hip", "swx_score.hip", "swx_testhooks.hip", "swx_gemm.hip", "swx_gemm_tiled.hip", "swx_gemm_big.hip", "swx_gemm_f32.hip", "swx_norm.hip", "swx_attn.hip", "swx_xattn.hip", "swx_selfattn.hip", "swx_decode.hip", "swx_align.hip",
            "swx_mel.hip", "swx_dtw.hip", "swx_decstep.hip", "swx_loudness.hip", "swx_headsel.hip", "swx_flac.hip", "swx_pcm.hip",
            "swx_denoise.hip"]
 

@@ -24,6 +24,9 @@ static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 // (no HIP calls: swx_test_lds_grants drives it on the host): per device 0..63 unknown (0), granted (1) or refused (-1).  Relaxed
 // atomics, no lock: two threads that both find "unknown" both set the attribute, which is harmless.  A device index outside 0..63
 // is never remembered (state 0: the attribute is set again on every launch).
+// The kernels: gemm_dec_f16, gemm_dectall_f16, self_attn_cached_mq_f16, attn_decode_cross_xq*_f16, attn_flash_f32, swx_dtw4_kernel,
+// swx_align_fused_kernel, and gemm_f16_ring<64, 3> (72 KB) / gemm_f16_ring<128, 3> (96 KB) / gemm_f16_big8 (128 KB) -- these three ran
+// ungranted through a bare launch until swx_gemm.hip was split (this ROCm let them; whether it needs the attribute was never measured).
 struct SwxLdsGrants {
     std::atomic<uint64_t> granted{0}, refused{0};
     static bool tracked(int dev) { return dev >= 0 && dev < 64; }

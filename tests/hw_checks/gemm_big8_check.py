@@ -1,4 +1,4 @@
-"""Hardware check of gemm_f16_big8 (csrc/swx_gemm.hip: the 256 x 256 tile on a ring of eight half-tile slots, force_kernel 12)
+"""Hardware check of gemm_f16_big8 (csrc/swx_gemm_big.hip: the 256 x 256 tile on a ring of eight half-tile slots, force_kernel 12)
 against the register-staged gemm_f16_tiled (1): the same MFMA sequence per accumulator, so both must agree BIT FOR BIT (first
 hardware run, with the two-stage generation it replaced as a third party: profiles/r04_big8_check.txt).  The kernel orders its LDS-DMA by counted waits and raw barriers between two staggered groups of waves; a
 misplaced wait would show as a rare wrong tile, not as a wrong kernel, so every shape is repeated REPS times on fresh NaN-filled

@@ -471,6 +471,21 @@ def test_new_kernel_paths_in_subprocess(check):
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-2000:])
 
 
+def test_gemm_lds_grant_first_launches_in_subprocess():
+    # gemm_f16_ring<64 | 128, 3> and gemm_f16_big8 ask for 72 / 96 / 128 KB of dynamic LDS and take their grant
+    # (swx_common.h::swx_launch_lds) on their first launch: a fresh process whose very first GEMM launches are those three, each
+    # returning 0 and bit-identical to the register-staged kernel at the smallest shapes with partial tiles and the shortest K loops
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    from conftest import subprocess_env
+    r = subprocess.run([sys.executable, os.path.join(here, "hw_checks", "gemm_first_launch_check.py")], capture_output=True, text=True,
+                       timeout=120, env=subprocess_env())
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-2000:])
+    assert r.stdout.count("ok   ") == 6, r.stdout[-3000:]
+
+
 # ------------------------------------------------------------------------------------- decode-step "dec" GEMM
 def _dec_scratch_bytes(M, N, K):
     return N * K * 2 + 8 * N + 16 * M * N * 4 + 8192 + 4096 * 4

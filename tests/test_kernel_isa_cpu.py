@@ -158,7 +158,7 @@ def _kernel_meta(src_name):
 
 @pytest.mark.parametrize("src,kernels,max_vgpr", [
     # the default tiled GEMMs: three workgroups per CU need <= 168 VGPRs and <= 53 KB of LDS each
-    ("swx_gemm.hip", ["gemm_f16_glds_128", "gemm_f16_glds_64"], 168),
+    ("swx_gemm_tiled.hip", ["gemm_f16_glds_128", "gemm_f16_glds_64"], 168),
     # DTW generation 3 (x chunks in registers) and the register-resident logit filters (1024 threads: <= 128 VGPRs)
     ("swx_dtw.hip", ["swx_dtw4_kernelILi1ELb1E", "swx_dtw4_kernelILi2ELb0E"], 256),
     ("swx_decode.hip", ["decode_select_reg_kernel"], 128),
@@ -176,13 +176,13 @@ def test_hot_kernels_do_not_spill(src, kernels, max_vgpr):
 
 
 def test_ring_gemm_k_loop_waits_are_the_counted_ones():
-    """gemm_f16_ring (csrc/swx_gemm.hip): the LDS-DMA of its operand ring is issued from inline asm and retired by hand --
+    """gemm_f16_ring (csrc/swx_gemm_tiled.hip): the LDS-DMA of its operand ring is issued from inline asm and retired by hand --
     `s_waitcnt vmcnt((NST - 2) * L) lgkmcnt(0)` + `s_barrier` per K step, L = DMA instructions per wave and stage.  Audited
     on the compiled ISA of both instantiations (64- and 128-column tiles, depth 3): (1) between the first DMA and the last MFMA every `vmcnt` wait is one of
     the asm statements (an `s_waitcnt vmcnt` hipcc adds on its own there would drain the ring); (2) their immediates are
     exactly {(NST - 2) L, ..., L, 0}; (3) every asm wait is followed by the barrier; (4) no scratch, and the K loop holds
     2 x 4 x NJ MFMAs per step."""
-    text = _device_asm("swx_gemm.hip")
+    text = _device_asm("swx_gemm_tiled.hip")
     seen = 0
     for bnt, nst in ((64, 3), (128, 3)):
         m = re.search(rf"^(_ZN\S*gemm_f16_ringILi{bnt}ELi{nst}E[^\s:]*):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M)
@@ -208,7 +208,7 @@ def test_ring_gemm_k_loop_waits_are_the_counted_ones():
                 waits.append(int(w.group(1)))
         assert sorted(set(waits)) == sorted({k * L for k in range(nst - 1)}), (bnt, nst, waits)
     assert seen == 2
-    meta = _kernel_meta("swx_gemm.hip")
+    meta = _kernel_meta("swx_gemm_tiled.hip")
     ring = {n: v for n, v in meta.items() if "gemm_f16_ring" in n}
     assert len(ring) == 2
     for n, v in ring.items():
@@ -216,13 +216,13 @@ def test_ring_gemm_k_loop_waits_are_the_counted_ones():
 
 
 def test_big8_gemm_phases():
-    """gemm_f16_big8 (the 256 x 256 tile kernel: a ring of eight half-tile slots, csrc/swx_gemm.hip): the compiled ISA must hold the schedule
+    """gemm_f16_big8 (the 256 x 256 tile kernel: a ring of eight half-tile slots, csrc/swx_gemm_big.hip): the compiled ISA must hold the schedule
     the ordering argument in the source is made for.  Three copies of a K tile (steady, second-last, last), each four phases of
     [fragment reads -> counted vmcnt -> barrier -> lgkmcnt(0) -> DMA issue -> 16 MFMAs -> barrier] with 12 / 4 / 8 / 0 reads; every
     `vmcnt` wait is one of the hand-written ones (10 after the prologue's 14 DMA instructions; 8, 8, -, 8 in the steady tile;
     8, 8, -, 4 and 2, 0, -, - in the last two); the DMA instructions of a phase come AFTER its first barrier (a slot is rewritten
     only once every wave has retired its reads of it) and its fragment reads BEFORE it; no scratch, <= 256 VGPRs."""
-    text = _device_asm("swx_gemm.hip")
+    text = _device_asm("swx_gemm_big.hip")
     m = re.search(r"^(_ZN\S*gemm_f16_big8E[^\s:]*):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M)
     assert m
     lines = [ln.strip() for ln in m.group(2).split("\n")]
@@ -274,7 +274,7 @@ def test_big8_gemm_phases():
     want += tile((8, 8, 8), (1, 1, 1, 1)) + tile((8, 8, 4), (1, 0, 0, 0)) + tile((2, 0, None), (0, 0, 0, 0))
     want += [("bar", 1)]                                                         # row group 0's extra barrier: the ring is the epilogue's now
     assert rle == want, [(a, b) for a, b in zip(rle, want) if a != b][:4]
-    meta = {n: v for n, v in _kernel_meta("swx_gemm.hip").items() if "gemm_f16_big8" in n}
+    meta = {n: v for n, v in _kernel_meta("swx_gemm_big.hip").items() if "gemm_f16_big8" in n}
     assert len(meta) == 1
     for n, v in meta.items():
         assert v["private_segment_fixed_size"] == 0 and v["vgpr_count"] <= 256, (n, v)
@@ -290,7 +290,7 @@ def test_f32_rows64_asm_loads_are_not_touched_before_their_wait():
     spec = importlib.util.spec_from_file_location("isa_asm_load_audit", os.path.join(ROOT, "scripts", "isa_asm_load_audit.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    lines = _device_asm("swx_gemm.hip").split("\n")
+    lines = _device_asm("swx_gemm_f32.hip").split("\n")
     for key in ("gemm_f32_rows64ILi1E", "gemm_f32_rows64ILi2E"):
         body = mod.kernel_body(lines, key)
         assert body is not None, key
